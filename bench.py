@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dataset raf|soundspaces] [--rays R --slices B]
     python bench.py --mode eval [--steps K --warmup W --rirs M]         (BASELINE configs[4]: full eval render, see EvalRender)
+    python bench.py ... --full                 (every side measurement of the full record, see below)
+    python bench.py ... --dump-outputs DIR     (what the last timed step computed, as DIR/<name>.npy; fixed-order sums)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A *step* is one pass of NeRAFPipeline.get_train_loss_dict (NeRAF_pipeline.py:166-222) + backward + optimizer steps over one
@@ -12,12 +14,13 @@ NeRAF_config.py:57,87); ``config.workload`` states exactly which stages are insi
 ``--scaling weak`` (default): every rank owns --rays / --slices of its own; ``--scaling strong``: --rays / --slices are the GLOBAL
 batch, split contiguously over the ranks.  Gradients and STFT-loss sums are all-reduced over RCCL.
 
-Rank 0 prints ONE COMPACT JSON line (< 6 KB, asserted: ``compact_line``): whole-job field-samples/s (and rays/s, bins/s),
-``roofline`` for the kernel family with the largest share of the step (HIP-event durations recorded inside the library over an
-instrumented replay of the same steps), ``cpu_baseline`` (the CPU oracle on this host, bounded sample of the same workload),
-``eval_render`` and ``parity`` in short.  The FULL record (every kernel family, every window, the notes) goes to the file the
-line names under ``detail`` (gpurun_out/bench_detail_*.json) -- round 5 printed it all on stdout, 22.7 KB, and the driver could
-not read the line.
+Rank 0 prints ONE COMPACT JSON line (< 6 KB, asserted: ``compact_line``): whole-job field-samples/s (and rays/s, bins/s) over
+exactly --steps timed steps after the set-up steps and the --warmup steps; nothing else runs.  With ``--full`` the value is the
+median of --repeats such windows and the line adds ``roofline`` for the kernel family with the largest share of the step (HIP-event
+durations recorded inside the library over an instrumented replay of the same steps), ``cpu_baseline`` (the CPU oracle on this
+host, bounded sample of the same workload), ``eval_render`` and ``parity`` in short; the FULL record (every kernel family, every
+window, the notes) goes to the file the line names under ``detail`` (--detail, or bench_detail_<mode>_n<N>.json in the output
+folder by default) -- round 5 printed it all on stdout, 22.7 KB, and the driver could not read the line.
 """
 import argparse
 import ctypes as C
@@ -90,6 +93,18 @@ def parse():
     ap.add_argument("--dataset", choices=("raf", "soundspaces"), default="raf",
                     help="audio head shape: raf = 1 x 513 bins, T = 60 (BASELINE configs[1..2], the default and the metric's config); "
                          "soundspaces = 2 x 257 bins, T = 101 (configs[3]: globally 32768 rays + 6464 slices, i.e. per GPU 4096 + 808)")
+    ap.add_argument("--full", action="store_true",
+                    help="the full record: besides the headline window, the --repeats windows (median headline), the fixed-batch and "
+                         "early-schedule windows, the replicated ResNet3D time, the instrumented replay (roofline), the eval_render line, "
+                         "trajectory parity and cpu_baseline, all written to the --detail file.  Without it a run sets up, warms up, times "
+                         "exactly --steps steps and prints the line; --repeats / --parity / --no-parity / --no-eval-line / "
+                         "--no-cpu-baseline / --detail act only with --full.  --plain takes precedence over it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB; larger arrays as a fixed seeded sample of their elements): train mode the loss and loss dict, every "
+                         "parameter after the optimizer step and its gradient; eval mode the frame's output images and the RIRs' raw "
+                         "outputs.  Such a run forms its sums in a fixed order (NERAF_DETERMINISTIC=1 unless the variable is set), so "
+                         "that two runs give the same arrays; its timed steps are slower than the default mode's fp32 atomics")
     return ap.parse_args()
 
 
@@ -144,7 +159,7 @@ def compact_line(full: dict, detail: str = None, limit: int = LINE_LIMIT) -> str
     cfg = full.get("config") or {}
     out["config"] = {"workload": _short(cfg.get("workload", ""), 200),
                      **_pick(cfg, ("rays_per_gpu", "slices_per_gpu", "global_rays", "global_slices", "rays_per_frame", "rirs_per_step",
-                                   "bins_per_rir", "parallelism", "distinct_resident_batches"))}
+                                   "bins_per_rir", "parallelism", "distinct_resident_batches", "deterministic"))}
     if (cfg.get("encoder_grid", 128), cfg.get("encoder_features", 1024)) != (128, 1024):
         out["config"].update(_pick(cfg, ("encoder_grid", "encoder_features")))
     if "roofline" in full:
@@ -227,6 +242,81 @@ def T(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE_CAPS = (1 << 18, 1 << 16, 1 << 14, 1 << 12)     # elements kept per array: the largest cap whose total fits the limit
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: ``arrays`` {name: tensor / ndarray / number} -> ``path``/<name>.npy, float64 stays float64, every other dtype
+    becomes float32.  An array with more elements than the cap is written as the elements at a fixed set of flat indices (numpy
+    generator seeded by ``seed`` and the name, sorted), so two runs with the same arguments write the same positions.  Returns
+    {name: (shape written, elements of the whole array)}."""
+    import zlib
+    import numpy as np
+    import torch
+    flat = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            flat[name] = (v.reshape(-1), tuple(v.shape), v.dtype == torch.float64)
+        else:
+            v = np.asarray(v)
+            flat[name] = (v.reshape(-1), v.shape, v.dtype == np.float64)
+
+    def nbytes(cap):
+        return sum(min(f.numel() if isinstance(f, torch.Tensor) else f.size, cap) * (8 if f64 else 4) for f, _, f64 in flat.values())
+    cap = next((c for c in DUMP_SAMPLE_CAPS if nbytes(c) <= DUMP_LIMIT_BYTES), None)
+    if cap is None:
+        raise SystemExit(f"--dump-outputs: {len(flat)} arrays exceed {DUMP_LIMIT_BYTES} bytes even at {DUMP_SAMPLE_CAPS[-1]} elements each")
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, (f, shape, f64) in flat.items():
+        n = f.numel() if isinstance(f, torch.Tensor) else f.size
+        if n > cap:
+            idx = np.sort(np.random.default_rng([seed, zlib.crc32(name.encode())]).choice(n, cap, replace=False))
+            f = f[torch.from_numpy(idx).to(f.device)] if isinstance(f, torch.Tensor) else f[idx]
+        else:
+            f = f.reshape(shape)
+        if isinstance(f, torch.Tensor):
+            f = f.to(torch.float64 if f64 else torch.float32).cpu().numpy()
+        else:
+            f = f.astype(np.float64 if f64 else np.float32)
+        np.save(os.path.join(path, name + ".npy"), f)
+        written[name] = (f.shape, n)
+    return written
+
+
+def _train_step_outputs(st):
+    """What the caller of the timed training step holds after it: the summed loss and the loss dict train_iteration returned, every
+    parameter of the two models as the optimizer steps left it, and its gradient (parameters without one this step have none)."""
+    loss, loss_dict = st.last
+    out = {"loss": loss}
+    out.update({"loss_dict." + k: v for k, v in loss_dict.items()})
+    seen = set()
+    for prefix, mod in (("vision", st.vm), ("audio", st.am)):
+        for k, p in mod.named_parameters():
+            if id(p) in seen:
+                continue
+            seen.add(id(p))
+            out[f"param.{prefix}.{k}"] = p
+            if p.grad is not None:
+                out[f"grad.{prefix}.{k}"] = p.grad
+    return out
+
+
+def _eval_step_outputs(er):
+    """What the caller of the timed eval step holds after it: the frame's output images and, of its RIRs, the raw log-magnitudes
+    [rirs, T, C, F] and the grid panels (the remaining panels are views of these and of the inputs)."""
+    out = {"frame." + k: v for k, v in er.last_frame.items()}
+    if er.last_rirs:
+        import torch
+        out["rir.raw_output"] = torch.stack([r["raw_output"] for r in er.last_rirs])
+        for k in ("grid", "grid_density"):
+            if k in er.last_rirs[-1]:
+                out["rir." + k] = er.last_rirs[-1][k]
+    return out
+
+
 class JointStep:
     """cfg3 (RAF FurnishedRoom joint) training step, NeRAFPipeline.get_train_loss_dict order (NeRAF_pipeline.py:175-199):
        1. NeRAFVisionModel.get_outputs on the ray batch (sampler, 2 proposal nets, 2 PDF resamplings, fused field
@@ -307,8 +397,8 @@ class JointStep:
 
     def step(self):
         self.i += 1
-        loss, _ = self.pipe.train_iteration(self.i, self.opt_wrapper, self.scaler)
-        return loss
+        self.last = self.pipe.train_iteration(self.i, self.opt_wrapper, self.scaler)
+        return self.last[0]
 
 
 class EvalRender:
@@ -367,8 +457,8 @@ class EvalRender:
 
     def step(self, rirs):
         out = self.frame()
-        for j in range(rirs):
-            self.rir(self.i * rirs + j)
+        self.last_frame = out
+        self.last_rirs = [self.rir(self.i * rirs + j) for j in range(rirs)]
         self.i += 1
         return out
 
@@ -474,9 +564,9 @@ def _prof_families(lib, h, local, nprof, ref_rows):
 GATHER_CEILING_GBS = 8600.0   # MI355X_MICROARCH.md "Indexed rows": 38 MB table, uniformly random rows served from the Infinity Cache
 
 
-def measure_eval(er, steps, warmup, rirs, lib, h, local, sync, full=True):
+def measure_eval(er, steps, warmup, rirs, lib, h, local, sync, full=True, after_timed=None):
     """Time `steps` eval steps (see EvalRender) after `warmup`; returns the measurement dict shared by `--mode eval` and the
-    `eval_render` key of the training line."""
+    `eval_render` key of the training line.  `after_timed()` runs right after the timed steps (outside the timed region)."""
     import torch
     for _ in range(max(warmup, 1)):
         er.step(rirs)
@@ -486,6 +576,8 @@ def measure_eval(er, steps, warmup, rirs, lib, h, local, sync, full=True):
         er.step(rirs)
     sync()
     el = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed()
     # the two halves on their own (the reference reports them separately: num_rays_per_sec / fps, num_rays_per_sec_audio / fps_audio)
     sync(); t1 = time.perf_counter()
     for _ in range(steps):
@@ -704,12 +796,13 @@ def trajectory_parity(dev, scenario="g9_long", floor_family=None):
     order probes) through the frozen rule trajectory_common.GATE_RULE.  tests/test_gpu_trajectory.py asserts the same on the
     deterministic run and on the median of five default-mode runs; this is ONE default-mode run, reported."""
     import numpy as np
-    fx = os.path.join(ROOT, "tests", "golden", scenario + ".npz")
-    if not os.path.exists(fx):
-        return None
     sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import golden_io
+    try:
+        g = golden_io.load(scenario)
+    except FileNotFoundError:
+        return None
     import trajectory_common as TC
-    g = np.load(fx)
     cfg = dict(TC.SCENARIOS[scenario], n_rir_eval=int(g["stft"].shape[0]))
     t0 = time.perf_counter()
     curves, img, stft, pipe, evb = TC.run_hip_trajectory(dev, cfg=cfg, fixed_scale=False)
@@ -774,6 +867,38 @@ def _family_regex(pattern: str):
     return re.compile("(?:" + "|".join(alts) + ")")
 
 
+def _deterministic():
+    """NERAF_DETERMINISTIC as the library reads it: fixed-order sums instead of fp32 atomics (--dump-outputs turns it on)."""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("NERAF_DETERMINISTIC", ""))      # atoi(e) != 0
+    return bool(m) and int(m.group()) != 0
+
+
+def _train_config(a, R_local, B_local, R_global, B_global, world):
+    """The ``config`` object of the training line (plain and --full runs alike)."""
+    return {
+        "workload": (("RAF FurnishedRoom joint training step (BASELINE configs[2]): %d rays + %d RIR slices x 513 bins per GPU" if a.dataset == "raf"
+                      else "SoundSpaces joint training step (BASELINE configs[3] head): %d rays + %d RIR slices x 2 x 257 bins per GPU")
+                     % (R_local, B_local)) + "; radiance + grid refresh + ResNet3D + NAcF + STFT loss, backward, GradScaler + fused Adam; batches resident"
+                    + ("" if (a.grid, a.n_features) == (128, 1024) else f"; NON-DEFAULT encoder: {a.grid}^3 grid, {a.n_features} features"),
+        "workload_detail": (("RAF FurnishedRoom joint step (BASELINE configs[2] shape: %d rays + %d RIR slices x 513 bins per GPU): " if a.dataset == "raf"
+                      else "SoundSpaces joint step (BASELINE configs[3] head shape: %d rays + %d RIR slices x 2 x 257 bins per GPU): ") +
+                     "radiance forward (camera-pose deltas, sampler, 2 proposal nets, 2 PDF resamplings, fused field query, composite) + rgb/"
+                     "interlevel/distortion losses -> grid refresh (%d cells x 18 dirs%s) -> ResNet3D forward on the 7x128^3 "
+                     "grid -> audio prologue + NAcF MLP -> STFT loss -> one backward (NAcF -> ResNet3D -> refreshed grid cells -> "
+                     "field; radiance losses -> proposal nets + fused field backward + weight-grad GEMMs) -> %sGradScaler + "
+                     "fused Adam: proposal_networks + fields (lr 1e-2 -> 1e-4 @200k), then audio_fields = NAcF + ResNet3D + fields again "
+                     "(lr 1e-4 -> 1e-8, 2000 warm-up), as NeRAF_pipeline.py:487 / NeRAF_config.py:115-132 group and schedule them -> "
+                     "scheduler steps; the camera optimizer (SO3xR3, NeRAF_config.py:97) is on: pose deltas applied to the ray bundle, "
+                     "their photometric + regulariser gradients computed, camera_opt Adam group stepped (lr 1e-3 -> 1e-4 @5k).  "
+                     "The steps cycle through %d distinct resident batches.  Not inside: data loading (batches are resident).")
+                     % (R_local, B_local, 4096, ", sharded over the ranks" if world > 1 else "", "RCCL all-reduce -> " if world > 1 else "",
+                        a.rotate),
+        "rays_per_gpu": R_local, "slices_per_gpu": B_local, "global_rays": R_global, "global_slices": B_global,
+        "parallelism": f"dp{world}", "distinct_resident_batches": a.rotate, "encoder_grid": a.grid, "encoder_features": a.n_features,
+        "deterministic": _deterministic(),
+    }
+
+
 def run_eval_mode(a, dev, rank, local, world):
     """`bench.py --mode eval`: BASELINE configs[4] (full eval render) as a throughput line -- see EvalRender for what a step is.
     N > 1: frames and RIRs are independent, every rank renders its own (the pipeline deals eval items round-robin, SURVEY 8e "Eval"):
@@ -795,7 +920,7 @@ def run_eval_mode(a, dev, rank, local, world):
     torch.cuda.synchronize()
     gc.collect()
     gc.freeze()
-    if a.plain:
+    if a.plain or not a.full:
         for _ in range(a.warmup):
             er.step(a.rirs)
         sync()
@@ -804,13 +929,27 @@ def run_eval_mode(a, dev, rank, local, world):
             er.step(a.rirs)
         sync()
         el = time.perf_counter() - t0
-        if rank == 0:
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, _eval_step_outputs(er))
+        if rank == 0 and a.plain:
             print(json.dumps({"metric": "field-samples/sec (rays + RIR STFT bins), eval render", "mode": "eval", "plain": True,
                               "value": (er.rays_per_frame + a.rirs * er.bins_per_rir) * a.steps * world / el, "unit": "field-samples/s",
                               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": el / a.steps * 1e3,
                               "steps_executed_in_process": 2 + a.warmup + a.steps, "rirs_per_step": a.rirs}))
+        elif rank == 0:
+            print(compact_line({"metric": "field-samples/sec (rays + RIR STFT bins), eval render", "mode": "eval",
+                                "value": (er.rays_per_frame + a.rirs * er.bins_per_rir) * a.steps * world / el, "unit": "field-samples/s",
+                                "n_gpus": world, "ranks_seen": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": el / a.steps * 1e3,
+                                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+                                "rirs_per_step": a.rirs,
+                                "config": {"workload": "BASELINE configs[4] (full eval render) per GPU, no grad: a step = one 684x1024 RAF frame "
+                                                       "(22 chunks of 32768 rays) + %d RIRs through the audio eval branch, scene feature cached" % a.rirs,
+                                           "rays_per_frame": er.rays_per_frame, "rirs_per_step": a.rirs, "bins_per_rir": er.bins_per_rir,
+                                           "parallelism": f"dp{world} (eval items dealt round-robin, no collective)",
+                                           "deterministic": _deterministic()}}, None), flush=True)
         return
-    m, fams = measure_eval(er, a.steps, a.warmup, a.rirs, lib, h, local, sync)
+    dump = (lambda: dump_outputs(a.dump_outputs, _eval_step_outputs(er))) if a.dump_outputs and rank == 0 else None
+    m, fams = measure_eval(er, a.steps, a.warmup, a.rirs, lib, h, local, sync, after_timed=dump)
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([m["ms_per_step"]], device=dev, dtype=torch.float64)
@@ -849,6 +988,13 @@ def run_eval_mode(a, dev, rank, local, world):
 
 def main():
     a = parse()
+    if a.dump_outputs and "NERAF_DETERMINISTIC" not in os.environ:
+        # the default mode adds BatchNorm statistics, bias / embedding gradients and scatters with fp32 atomics in the order the hardware
+        # runs them, and the encoder's ReLU gates turn those last-bit differences into different gradients from the first step on (a
+        # few % in single entries, more after the priming steps): two runs would part by far more than rounding.  The run whose
+        # outputs are compared forms every such sum in a fixed order instead (csrc/common.h neraf_deterministic; the library reads
+        # the variable once, before the first launch -- set here before anything is loaded and inherited by spawned ranks).
+        os.environ["NERAF_DETERMINISTIC"] = "1"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(a))
@@ -859,6 +1005,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     assert torch.cuda.is_available(), "bench.py needs MI355X GPUs (no CPU fallback)"
+    torch.manual_seed(0)        # the modules' own initialisers and the sampler's jitter stream: the same inputs in every run
     # NERAF_BENCH_SHARE_GPU=1 (test aid): several ranks share the visible GPUs and talk over gloo -- exercises the multi-rank
     # code path (sharding, overlapped gradient reducer, global loss sums) on a 1-GPU box; never a measurement.
     share = os.environ.get("NERAF_BENCH_SHARE_GPU") == "1"
@@ -936,7 +1083,9 @@ def main():
 
     elapsed = timed_steps(a.steps)
     # the same window again, `--repeats` times: 20 steps are 87 ms -- one sample; the spread says how much to trust it
-    repeat_ms = [elapsed / a.steps * 1e3] + ([timed_steps(a.steps) / a.steps * 1e3 for _ in range(max(a.repeats - 1, 0))] if not a.plain else [])
+    repeat_ms = [elapsed / a.steps * 1e3] + ([timed_steps(a.steps) / a.steps * 1e3 for _ in range(max(a.repeats - 1, 0))] if a.full and not a.plain else [])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, _train_step_outputs(st))
 
     if a.plain:
         if rank == 0:
@@ -948,6 +1097,22 @@ def main():
                               "config": {"rays_per_gpu": R_local, "slices_per_gpu": B_local, "global_rays": R_global,
                                          "global_slices": B_global, "parallelism": f"dp{world}", "dataset": a.dataset},
                               "steps_executed_in_process": PRIME_STEPS + a.warmup + a.steps}))
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+
+    if not a.full:
+        # the headline alone: the one window of exactly --steps steps (the --full run reports the median of --repeats such windows)
+        if rank == 0:
+            bins = B_global * C_ * F_
+            out = {"metric": "field-samples/sec (rays + RIR STFT bins)", "value": (R_global + bins) * a.steps / elapsed, "unit": "field-samples/s",
+                   "n_gpus": world, "ranks_seen": ranks_seen, "backend": backend, "steps": a.steps, "warmup": a.warmup,
+                   "priming_steps": PRIME_STEPS + CLOCK_STEPS, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
+                   "scaling": a.scaling, "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+                   "rays_per_s": R_global * a.steps / elapsed, "bins_per_s": bins * a.steps / elapsed,
+                   "config": _train_config(a, R_local, B_local, R_global, B_global, world)}
+            print(compact_line(out, None), flush=True)
         if world > 1:
             import torch.distributed as dist
             dist.destroy_process_group()
@@ -1080,28 +1245,8 @@ def main():
             "replicated_per_rank": {"resnet3d_fwd_bwd_ms": resnet_ms,
                                     "note": "data parallel: the ResNet3D forward + backward runs on every rank (the grid and its weights are "
                                             "replicated); rays, RIR slices and the grid-refresh cells are sharded"},
-            "config": {
-                "workload": (("RAF FurnishedRoom joint training step (BASELINE configs[2]): %d rays + %d RIR slices x 513 bins per GPU" if a.dataset == "raf"
-                              else "SoundSpaces joint training step (BASELINE configs[3] head): %d rays + %d RIR slices x 2 x 257 bins per GPU")
-                             % (R_local, B_local)) + "; radiance + grid refresh + ResNet3D + NAcF + STFT loss, backward, GradScaler + fused Adam; batches resident"
-                            + ("" if (a.grid, a.n_features) == (128, 1024) else f"; NON-DEFAULT encoder: {a.grid}^3 grid, {a.n_features} features"),
-                "workload_detail": (("RAF FurnishedRoom joint step (BASELINE configs[2] shape: %d rays + %d RIR slices x 513 bins per GPU): " if a.dataset == "raf"
-                              else "SoundSpaces joint step (BASELINE configs[3] head shape: %d rays + %d RIR slices x 2 x 257 bins per GPU): ") +
-                             "radiance forward (camera-pose deltas, sampler, 2 proposal nets, 2 PDF resamplings, fused field query, composite) + rgb/"
-                             "interlevel/distortion losses -> grid refresh (%d cells x 18 dirs%s) -> ResNet3D forward on the 7x128^3 "
-                             "grid -> audio prologue + NAcF MLP -> STFT loss -> one backward (NAcF -> ResNet3D -> refreshed grid cells -> "
-                             "field; radiance losses -> proposal nets + fused field backward + weight-grad GEMMs) -> %sGradScaler + "
-                             "fused Adam: proposal_networks + fields (lr 1e-2 -> 1e-4 @200k), then audio_fields = NAcF + ResNet3D + fields again "
-                             "(lr 1e-4 -> 1e-8, 2000 warm-up), as NeRAF_pipeline.py:487 / NeRAF_config.py:115-132 group and schedule them -> "
-                             "scheduler steps; the camera optimizer (SO3xR3, NeRAF_config.py:97) is on: pose deltas applied to the ray bundle, "
-                             "their photometric + regulariser gradients computed, camera_opt Adam group stepped (lr 1e-3 -> 1e-4 @5k).  "
-                             "The steps cycle through %d distinct resident batches.  Not inside: data loading (batches are resident).")
-                             % (R_local, B_local, 4096, ", sharded over the ranks" if world > 1 else "", "RCCL all-reduce -> " if world > 1 else "",
-                                a.rotate),
-                "rays_per_gpu": R_local, "slices_per_gpu": B_local, "global_rays": R_global, "global_slices": B_global,
-                "parallelism": f"dp{world}", "distinct_resident_batches": a.rotate, "encoder_grid": a.grid, "encoder_features": a.n_features,
-                "repeat_windows_ms_per_step": {"n": len(repeat_ms), "median": _median(repeat_ms), "min": min(repeat_ms), "max": max(repeat_ms)},
-            },
+            "config": dict(_train_config(a, R_local, B_local, R_global, B_global, world),
+                           repeat_windows_ms_per_step={"n": len(repeat_ms), "median": _median(repeat_ms), "min": min(repeat_ms), "max": max(repeat_ms)}),
         }
         if dom:
             out["roofline"] = {"bound": dom["bound"], "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": dom["peak"],

@@ -7,6 +7,9 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+TOOLS = os.path.join(ROOT, "tests", "tools")
+if TOOLS not in sys.path:
+    sys.path.insert(0, TOOLS)
 
 
 def pytest_configure(config):
@@ -15,8 +18,8 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    import golden_io       # tests/tools/golden_io.py: <name>.npz, or the <name>.part<K>.npz files of a fixture stored in parts
 
     def load(name):
-        return np.load(os.path.join(GOLDEN, name + ".npz"))
+        return golden_io.load(name, GOLDEN)
     return load

@@ -74,3 +74,28 @@ def test_profile_references_are_named_files_that_exist():
         assert os.path.exists(os.path.join(ROOT, "profiles", name)), (k, name)
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "glob.glob" not in src                               # no "newest file wins" citation (round 5: sorted(glob)[-1])
+
+
+def test_dump_outputs_dtypes_sampling_and_budget(tmp_path):
+    """--dump-outputs (CPU tensors stand in for the device's): float64 stays float64, other dtypes become float32, arrays above the
+    per-array cap are a sorted, seeded sample that is the same in every call, and the files together stay within 64 MB."""
+    import numpy as np
+    import torch
+    big = torch.arange(3 << 20, dtype=torch.float32)
+    arrays = {"loss": torch.tensor(1.5), "h": torch.ones(7, 3, dtype=torch.float16), "d": np.arange(5, dtype=np.float64), "big": big,
+              "big_f64": big.double()}
+    w = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    assert a["loss"].dtype == np.float32 and a["loss"].shape == () and float(a["loss"]) == 1.5
+    assert a["h"].dtype == np.float32 and a["h"].shape == (7, 3) and a["d"].dtype == np.float64
+    assert a["big"].size == bench.DUMP_SAMPLE_CAPS[0] < big.numel() and w["big"][1] == big.numel()
+    assert (np.diff(a["big"]) > 0).all()                       # the values of `arange` at sorted, distinct indices
+    for k in arrays:
+        assert np.array_equal(a[k], np.load(str(tmp_path / "b" / (k + ".npy"))))
+    total = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    assert total <= bench.DUMP_LIMIT_BYTES
+    many = {f"p{i}": big for i in range(80)}                   # 80 x 1 MB at the first cap: the next smaller cap is taken
+    bench.dump_outputs(str(tmp_path / "c"), many)
+    total = sum(os.path.getsize(str(tmp_path / "c" / f)) for f in os.listdir(str(tmp_path / "c")))
+    assert total <= bench.DUMP_LIMIT_BYTES and np.load(str(tmp_path / "c" / "p0.npy")).size == bench.DUMP_SAMPLE_CAPS[1]

@@ -3,7 +3,7 @@ first N > 1 launch of today's bench.py must not happen on the driver's 8-GPU nod
 gloo (NERAF_BENCH_SHARE_GPU=1: never a measurement), started by bench.py itself the way the driver's launcher would start them
 (`python bench.py --gpus 2` spawns `torch.distributed.run --nproc-per-node 2`), in a fresh child process:
   * weak scaling, --plain: the line reports n_gpus = ranks_seen = 2, the backend, twice the per-rank batch as the global batch;
-  * strong scaling, the FULL line (instrumented replay, roofline, emit): the global batch is the command line's, split over the ranks."""
+  * strong scaling, the FULL line (--full: instrumented replay, roofline, emit): the global batch is the command line's, split over the ranks."""
 import json
 import os
 import subprocess
@@ -40,7 +40,7 @@ def test_two_rank_weak_scaling_plain_line(tmp_path):
 def test_two_rank_strong_scaling_full_line(tmp_path):
     detail = str(tmp_path / "detail.json")
     d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", "strong", "--rays", "2048", "--slices", "1024", "--repeats", "2",
-                "--parity", "off", "--no-eval-line", "--no-cpu-baseline", "--detail", detail], tmp_path)
+                "--full", "--parity", "off", "--no-eval-line", "--no-cpu-baseline", "--detail", detail], tmp_path)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["backend"] == "gloo" and d["scaling"] == "strong"
     c = d["config"]
     assert c["rays_per_gpu"] == 1024 and c["slices_per_gpu"] == 512 and c["global_rays"] == 2048 and c["global_slices"] == 1024

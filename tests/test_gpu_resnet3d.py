@@ -99,15 +99,11 @@ def test_resnet3d_variants_forward_vs_reference_golden(golden, S, N):
     assert rs <= (0.3 if N == 2048 else 0.1)        # element level at the last layer (not a mean over voxels): layout bugs read ~1.4
 
 
-@pytest.mark.parametrize("S,N", [(128, 2048), (256, 1024)])
-def test_resnet3d_variants_backward_norms_vs_reference_golden(golden, S, N):
-    """Backward of the variants against the REFERENCE's fp32 gradients, in the form that survives the gate flips of a chaotic
-    BatchNorm network (see test_resnet3d_backward_norms_vs_reference_fp32_golden): every parameter gradient finite, gradient norms
-    within 10 % (d gamma of the stem: 20 %), the grid gradient's rms within 10 % (single entries of an ungated comparison are chaos: the
-    sampled grid-gradient entries of the 256^3 run correlate -0.3 ... 0.0 with the fp32 reference's while the gate-matched test
-    below agrees on all 16.7 M cells to 2e-2).  Element-wise parity: test_resnet3d_backward_gate_matched[128-2048] / [256-1024]."""
+def _variant_backward_ratios(S, N):
+    """Norm ratios (HIP / reference fp32) of the variant encoder's gradients, see the test below; needs NERAF_DETERMINISTIC=1 in the
+    process environment to be reproducible."""
     dev = torch.device("cuda:0")
-    g = golden(f"g1_resnet3d_{S}_{N}")
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"g1_resnet3d_{S}_{N}.npz"))
     net = _model(dev, 1 / S, N)
     net.train()
     bb = net.backbone_net
@@ -140,6 +136,30 @@ def test_resnet3d_variants_backward_norms_vs_reference_golden(golden, S, N):
     dx = got["dx"].reshape(7, -1).cpu()
     if n_win == S ** 3:
         ratios["d grid rms"] = rms(dx) / g["dx_stats"][2]
+    return {k: float(v) for k, v in ratios.items()}
+
+
+@pytest.mark.parametrize("S,N", [(128, 2048), (256, 1024)])
+def test_resnet3d_variants_backward_norms_vs_reference_golden(S, N):
+    """Backward of the variants against the REFERENCE's fp32 gradients, in the form that survives the gate flips of a chaotic
+    BatchNorm network (see test_resnet3d_backward_norms_vs_reference_fp32_golden): every parameter gradient finite, gradient norms
+    within 10 % (d gamma of the stem: 20 %), the grid gradient's rms within 10 % (single entries of an ungated comparison are chaos: the
+    sampled grid-gradient entries of the 256^3 run correlate -0.3 ... 0.0 with the fp32 reference's while the gate-matched test
+    below agrees on all 16.7 M cells to 2e-2).  Element-wise parity: test_resnet3d_backward_gate_matched[128-2048] / [256-1024].
+    The run executes in a fresh process with NERAF_DETERMINISTIC=1 (fixed-order sums, the same bits every time), so the bounds are
+    single-run bounds: in the default mode the stem's d gamma ratio of the 128^3 / 2048 configuration varies from run to run with the
+    order of the BatchNorm statistics' atomic sums (1.14 ... 1.24 in five runs), across its bound."""
+    import json
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import json, sys; sys.path[:0] = [%r, %r]; import test_gpu_resnet3d as t; "
+            "print('RATIOS ' + json.dumps(t._variant_backward_ratios(%d, %d)))" % (os.path.dirname(here), here, S, N))
+    env = dict(os.environ, NERAF_DETERMINISTIC="1")
+    p = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0, out[-4000:]
+    ratios = json.loads(next(ln for ln in out.splitlines() if ln.startswith("RATIOS "))[len("RATIOS "):])
     print(f"ResNet3D S={S} N_features={N} backward / reference fp32:", {k: round(v, 3) for k, v in ratios.items()})
     for k, v in ratios.items():
         lo, hi = (0.8, 1.2) if k == "dgamma bn1" else (0.9, 1.1)

@@ -346,9 +346,10 @@ def test_long_trajectory_metric_parity(golden, tmp_path_factory, scenario):
     CPU per oracle run, NeRAF_config.py:78's 400k iterations in miniature).  The system is chaotic far beyond ~100 iterations, so
     tensors are not comparable -- metrics are, through THE RULE above.  One deterministic run.  Loss-curve tails (last 50 iterations):
     not above the fp32 oracle's by more than 15 %, within 45 % either way (unchanged from round 5)."""
+    import golden_io
     import trajectory_common as TC
-    if not os.path.exists(os.path.join(os.path.dirname(__file__), "golden", scenario + ".npz")):
-        pytest.skip(f"fixture tests/golden/{scenario}.npz not generated (tests/tools/gen_trajectory.py, ~2 h of CPU per oracle run)")
+    if not golden_io.exists(scenario):
+        pytest.skip(f"fixture tests/golden/{scenario} not generated (tests/tools/gen_trajectory.py, ~2 h of CPU per oracle run)")
     g = golden(scenario)
     cfg = TC.SCENARIOS[scenario]
     assert int(g["steps"]) == cfg["steps"] == 1000 and int(g["camera_opt"]) == int(bool(cfg["camera_opt"]))
@@ -389,9 +390,10 @@ def test_default_mode_long_trajectory_median(golden, tmp_path_factory, scenario)
     metric's mean inside the oracle family's own range, T60 sd 0.95 points, 2 of 24 single runs above the T60 gate): the median of
     three estimates the mode's median with a ~2 % chance of landing outside by chance, the median of five ~0.5 %.  Rule and gates
     are untouched; a larger sample is the stricter estimator (a mode whose true median is outside fails MORE surely)."""
+    import golden_io
     import trajectory_common as TC
-    if not os.path.exists(os.path.join(os.path.dirname(__file__), "golden", scenario + ".npz")):
-        pytest.skip(f"fixture tests/golden/{scenario}.npz not generated")
+    if not golden_io.exists(scenario):
+        pytest.skip(f"fixture tests/golden/{scenario} not generated")
     g = golden(scenario)
     # sample size by the measured single-run exceedance: G10 2 of 24 runs outside -> five; G9 none of 28 -> three
     tags = ("a", "b", "c", "d", "e") if scenario == "g10_long_pose" else ("a", "b", "c")

@@ -15,7 +15,8 @@ from neraf_amd.model import NeRAFAudioModel, NeRAFAudioModelConfig
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 SC = sys.argv[2] if len(sys.argv) > 2 else "g9_long"
-g = np.load(os.path.join(ROOT, "tests", "golden", SC + ".npz"))
+import golden_io
+g = golden_io.load(SC)
 cfg = TC.SCENARIOS[SC]
 runs = {}
 tmp = tempfile.mkdtemp()

@@ -15,7 +15,8 @@ from neraf_amd import synth
 from neraf_amd.model import NeRAFAudioModel, NeRAFAudioModelConfig
 
 SC = sys.argv[1] if len(sys.argv) > 1 else "g9_long"
-g = np.load(os.path.join(ROOT, "tests", "golden", SC + ".npz"))
+import golden_io
+g = golden_io.load(SC)
 cfg = TC.SCENARIOS[SC]
 dev = torch.device("cuda:0")
 am = NeRAFAudioModel(NeRAFAudioModelConfig(dataset="RAF", grid_step=1 / 64), TC.T(synth.audio_aabb())).to(dev)

@@ -22,9 +22,11 @@ def main():
     import trajectory_common as TC
     torch.manual_seed(0)
     cfg = TC.SCENARIOS[scenario]
-    fx = os.path.join(ROOT, "tests", "golden", scenario + ".npz")
-    if os.path.exists(fx):          # evaluate the held-out RIRs the committed fixture holds (the bank is prefix-stable: RIR i is RIR i for any count)
-        cfg = dict(cfg, n_rir_eval=int(np.load(fx)["stft"].shape[0]))
+    import golden_io
+    try:                            # evaluate the held-out RIRs the committed fixture holds (the bank is prefix-stable: RIR i is RIR i for any count)
+        cfg = dict(cfg, n_rir_eval=int(golden_io.load(scenario)["stft"].shape[0]))
+    except FileNotFoundError:
+        pass
     # the 100-iteration fixtures stay below the GradScaler's growth interval (asserted); the long one runs through it like a real run
     curves, img, stft, pipe, evb = TC.run_hip_trajectory(dev, cfg=cfg, fixed_scale=cfg["steps"] <= 100)
     extra = {}

@@ -1,15 +1,19 @@
 #!/bin/bash
-mkdir -p gpurun_out
+# The full bench line with its per-kernel-family table, then rocprofv3 --kernel-trace --stats of the same command.
+# Output folder: $OUT (default tool_out/).
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/tool_out}
+cd "$R"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-echo "== bench" ; timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+echo "== bench" ; timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --detail "$OUT/bench_detail_train_n1.json" > /dev/null 2>&1
+python - "$OUT/bench_detail_train_n1.json" <<'PY'
 import sys, json
-d = json.loads(sys.stdin.read())
+d = json.load(open(sys.argv[1]))
 print('ms_per_step', d['ms_per_step'], 'value', d['value'])
 for k in d['roofline']['all_kernel_families']:
-    print(f\"  {k['kernel'][:50]:50s} {k['launches_per_step']:6.1f}/step avg {k['avg_us']:8.1f} us  {k['ms_per_step']:6.3f} ms/step  {k['achieved']:8.1f} {k['unit']}\")
-"
-echo "== rocprof" ; cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/rocprof.log 2>&1
-cd $GRAFT_REPO_ROOT; f=$(find gpurun_out/prof -name "*kernel_stats.csv" | sort | tail -1); echo "stats: $f"; python - "$f" <<'PY'
+    print(f"  {k['kernel'][:50]:50s} {k['launches_per_step']:6.1f}/step avg {k['avg_us']:8.1f} us  {k['ms_per_step']:6.3f} ms/step  {k['achieved']:8.1f} {k['unit']}")
+PY
+echo "== rocprof" ; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --detail "$OUT/bench_detail_prof.json" > "$OUT/rocprof.log" 2>&1)
+f=$(find "$OUT/prof" -name "*kernel_stats.csv" | sort | tail -1); echo "stats: $f"; python - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)

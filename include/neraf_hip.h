@@ -84,6 +84,17 @@ int neraf_gemm_f16(neraf_ctx* ctx, const void* A, int lda, const void* B, int ld
                    void* C16, int ldc16, void* C16T, int ldc16t, float* C32, int ldc32,
                    neraf_stream_t stream);
 
+/* Grouped form: 1 to 6 contractions C32_g[M_g, N_g] (+)= alpha * alpha_dev[0] * A_g . B_g^T that share K, lda and ldb run as ONE grid
+ * (how the NAcF backward issues its narrow weight gradients and the radiance field its five; groups may differ in shape; exported
+ * for tests).  fp32 results only,
+ * no bias / activation.  A_g has >= round_up(M_g, 64) rows, B_g >= round_up(N_g, 64) rows; alpha_dev is an optional device scalar;
+ * c32_beta != 0 adds to C32 instead of overwriting it.  splitk_ws (optional fp32 scratch of splitk_bytes) lets a launch of few
+ * equal-shape tiles with a long K be split along K, as a single launch with scratch is.  Every result equals, bit for bit, that of
+ * the group's own launch (with scratch: where both are cut into the same number of K slices). */
+int neraf_gemm_f16_grouped(neraf_ctx* ctx, int ngroups, const void* const* A, const void* const* B, const int* M, const int* N,
+                           float* const* C32, const int* ldc32, int lda, int ldb, int K, float alpha, const float* alpha_dev,
+                           int c32_beta, void* splitk_ws, size_t splitk_bytes, neraf_stream_t stream);
+
 /* The same contraction with bfloat16 operands / 16-bit results (used by the deep gradient chains). */
 int neraf_gemm_bf16(neraf_ctx* ctx, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
                     int Mpad, int Npad, float alpha, const float* bias, int act,

@@ -235,11 +235,15 @@ struct GemmParams {
   double alg_flops;                  // ALGORITHMIC FLOPs of the operation this GEMM implements (a convolution's
                                      // 2 dout^3 taps cin cout, also for its transposed form); 0 = 2 M N K.  Profiling only.
   int bf16;                          // 1: every 16-bit operand/result (A, B, lmask, add16, C16, C16T) is bfloat16 (exported for tests)
-  // grouped launch (plain loader, fp32 results only): ngroups > 1 runs ngroups GEMMs of identical padded shape (Mpad, Npad, K,
-  // lda, ldb) in one grid; group g takes A/B/C32/M/N/ldc32 from grp[g].  Used for the small-output weight gradients.
+  // grouped launch (plain loader, fp32 results only): ngroups > 1 runs ngroups GEMMs that share K, lda and ldb in one grid; group g
+  // takes A/B/C32/M/N/ldc32 from grp[g].  Its operands have M and N rounded up to 64 rows (Mpad / Npad of the launch are not used for
+  // it); the tile shape is chosen from the launch's total tile count, tile_begin (set by the launcher) is the group's first tile in
+  // that shape, and a workgroup finds its group by walking this table.  Only groups of equal padded shape are split along K.  Used
+  // for the small-output weight gradients, each of which alone under-fills the chip and pays a launch floor.
   int ngroups;
-  struct Group { const half_t* A; const half_t* B; float* C32; int M, N, ldc32; } grp[6];
+  struct Group { const half_t* A; const half_t* B; float* C32; int M, N, ldc32; int tile_begin; } grp[6];
 };
+constexpr int kMaxGemmGroups = 6;
 
 int launch_gemm_f16(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream);
 

@@ -306,7 +306,8 @@ struct PipeTile {
 // two 32-deep halves (half the fragment reads and MFMAs per wave and K-step), the 512 threads stage half the chunks each, and the pair's
 // accumulators are added through the (idle) ring before the unchanged 4-wave epilogue.  For the K-loops that run one or two waves per
 // SIMD behind a long per-K-step issue chain (the implicit-GEMM convolutions), as for wgrad_wide_tn_kernel (profiles/r06_wgrad_waves_ab.txt).
-template <int BM, int BN, int NST, int LOADER, int KS, bool BF, bool TC = false, int NW = 4>
+// GRP: the grouped form (GemmParams::ngroups > 1), an instantiation of its own so that the ordinary launches carry none of its code.
+template <int BM, int BN, int NST, int LOADER, int KS, bool BF, bool TC = false, int NW = 4, bool GRP = false>
 __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p, int splits) {
   using T = Tile<BM, BN>;
   using E8 = typename ET<BF>::v8;
@@ -324,10 +325,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
   const int wm = wave >> 1, wn = wave & 1;
 
   // ---- XCD-aware tile mapping (bijective for any tile count) + split-K slice
-  const int tiles_m = p.Mpad / BM, tiles_n = p.Npad / BN;
-  const int ntiles = tiles_m * tiles_n;
-  const int ngroups = p.ngroups > 1 ? p.ngroups : 1;
-  const int nblocks = ntiles * splits * ngroups;
+  int tiles_m = p.Mpad / BM, tiles_n = p.Npad / BN;
+  const int nblocks = GRP ? (int)gridDim.x : tiles_m * tiles_n * splits;
   int bid = blockIdx.x;
   {
     const int q = nblocks >> 3, r = nblocks & 7;
@@ -336,9 +335,14 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
   }
   const half_t* Ag = p.A; const half_t* Bg0 = p.B;
   float* C32g = p.C32; int Mg = p.M, Ng = p.N, ldc32g = p.ldc32, grp = 0;
-  if (ngroups > 1) {
-    grp = bid / (ntiles * splits); bid -= grp * ntiles * splits;
-    Ag = p.grp[grp].A; Bg0 = p.grp[grp].B; C32g = p.grp[grp].C32; Mg = p.grp[grp].M; Ng = p.grp[grp].N; ldc32g = p.grp[grp].ldc32;
+  if constexpr (GRP) {
+    // the groups' tiles lie one group after another (tile-prefix table in the kernel arguments): this workgroup's group, then its
+    // tile within the group's own tiles_m x tiles_n
+    while (grp + 1 < p.ngroups && bid >= p.grp[grp + 1].tile_begin * splits) ++grp;
+    const GemmParams::Group& G = p.grp[grp];
+    bid -= G.tile_begin * splits;
+    tiles_m = (G.M + BM - 1) / BM; tiles_n = (G.N + BN - 1) / BN;
+    Ag = G.A; Bg0 = G.B; C32g = G.C32; Mg = G.M; Ng = G.N; ldc32g = G.ldc32;
   }
   const int split = bid % splits;      // the slices of one tile are neighbours -> same XCD, shared panels
   bid /= splits;
@@ -833,16 +837,24 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p, int sp
 // manifest records (neraf_manifest_enable) of one GEMM launch and, with split-K, of its reducer: operands once (an implicit-GEMM
 // convolution reads its source tensor once, not once per tap), results once; the K-split slabs where they are written and read
 static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int splits, int bm, int bn, double flops, bool wide = false) {
-  const double out_elems = (double)p.M * p.N;
-  const double rA = loader == 0 ? (double)p.M * p.K * 2.0 : (double)p.conv.din * p.conv.din * p.conv.din * p.conv.cin * 2.0;
-  const double rB = (double)p.N * p.K * 2.0;
+  double out_elems = (double)p.M * p.N;
+  double rA = loader == 0 ? (double)p.M * p.K * 2.0 : (double)p.conv.din * p.conv.din * p.conv.din * p.conv.cin * 2.0;
+  double rB = (double)p.N * p.K * 2.0;
+  const int ng = p.ngroups > 1 ? p.ngroups : 1;
+  if (ng > 1) {                   // a grouped launch: every group's operands and results
+    out_elems = rA = rB = 0.0;
+    for (int g = 0; g < ng; ++g) { out_elems += (double)p.grp[g].M * p.grp[g].N; rA += (double)p.grp[g].M * p.K * 2.0; rB += (double)p.grp[g].N * p.K * 2.0; }
+  }
   const double epi_r = out_elems * 2.0 * ((p.add16 ? 1 : 0) + (p.lmask ? 1 : 0) + (p.bnb_mask ? 1 : 0) + (p.bnb_x ? 1 : 0));
   const double epi_w = out_elems * (2.0 * ((p.C16 ? 1 : 0) + (p.C16T ? 1 : 0)) + (p.C32 ? 4.0 : 0.0));
-  const double slabs = (double)splits * p.Mpad * p.Npad * 4.0;
+  const double slabs = (double)splits * ng * p.Mpad * p.Npad * 4.0;
   char nm[96];
   // "<rocprofv3 kernel-name prefix> | description": the tool matches the prefix against the trace
-  snprintf(nm, sizeof(nm), "%s<%d, %d | %s M=%d N=%d K=%d%s", wide ? "gemm_f16_nt_wide_kernel" : "gemm_f16_nt_pipe_kernel", bm, bn,
-           loader == 0 ? "plain" : (p.conv.tflip ? "dgrad" : "conv"), p.M, p.N, p.K, splits > 1 ? " splitK" : "");
+  if (ng > 1)
+    snprintf(nm, sizeof(nm), "gemm_f16_nt_pipe_kernel<%d, %d | plain, %d groups, %.0f results K=%d%s", bm, bn, ng, out_elems, p.K, splits > 1 ? " splitK" : "");
+  else
+    snprintf(nm, sizeof(nm), "%s<%d, %d | %s M=%d N=%d K=%d%s", wide ? "gemm_f16_nt_wide_kernel" : "gemm_f16_nt_pipe_kernel", bm, bn,
+             loader == 0 ? "plain" : (p.conv.tflip ? "dgrad" : "conv"), p.M, p.N, p.K, splits > 1 ? " splitK" : "");
   if (splits > 1) {
     neraf_node(ctx, nm, flops, rA + rB, slabs);
     neraf_node(ctx, "splitk_reduce_kernel | K-split slabs -> result", 0.0, slabs + epi_r, epi_w);
@@ -851,17 +863,26 @@ static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int s
   }
 }
 
-template <int BM, int BN, int NST, int LOADER, int KS, bool BF, bool TC = false, int NW = 4>
-int launch_pipe(neraf_ctx* ctx, const GemmParams& p, int splits, hipStream_t stream) {
+template <int BM, int BN, int NST, int LOADER, int KS, bool BF, bool TC = false, int NW = 4, bool GRP = false>
+int launch_pipe(neraf_ctx* ctx, const GemmParams& p_in, int splits, hipStream_t stream) {
   using PT = PipeTile<BM, BN, NST>;
+  GemmParams p = p_in;
+  if ((p.ngroups > 1) != GRP) return neraf_fail(ctx, NERAF_EINVAL, "gemm: grouped launches take the grouped instantiation");
+  int grp_tiles = 0;
+  if (GRP) {          // tile-prefix table of the groups in this tile shape
+    for (int g = 0; g < p.ngroups; ++g) {
+      p.grp[g].tile_begin = grp_tiles;
+      grp_tiles += ((p.grp[g].M + BM - 1) / BM) * ((p.grp[g].N + BN - 1) / BN);
+    }
+  }
   static bool attr_set = false;
   if (!attr_set) {
-    NERAF_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_nt_pipe_kernel<BM, BN, NST, LOADER, KS, BF, TC, NW>),
+    NERAF_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_nt_pipe_kernel<BM, BN, NST, LOADER, KS, BF, TC, NW, GRP>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, PT::LDS_BYTES));
     attr_set = true;
   }
-  const int ntiles = (p.Mpad / BM) * (p.Npad / BN);
   const int ng = p.ngroups > 1 ? p.ngroups : 1;
+  const int ntiles = GRP ? grp_tiles : (p.Mpad / BM) * (p.Npad / BN);
   // executed: what the grid multiplies (padded K, zero-page taps of a convolution's faces); algorithmic: the operation's own count
   double flops = 2.0 * p.M * p.N * p.K;
   if (ng > 1) { flops = 0.0; for (int g = 0; g < ng; ++g) flops += 2.0 * p.grp[g].M * p.grp[g].N * p.K; }
@@ -871,7 +892,7 @@ int launch_pipe(neraf_ctx* ctx, const GemmParams& p, int splits, hipStream_t str
                       : LOADER == 1 ? (BM * BN == 128 * 128 ? PROF_CONV128 : (BM == 128 ? PROF_CONV12864 : (BF ? PROF_CONV64_BF16 : PROF_CONV)))
                                     : (BM * BN == 128 * 128 ? PROF_GEMM128 : (BM == 128 ? PROF_GEMM12864 : (BF ? PROF_GEMM64_BF16 : PROF_GEMM64)));
   ProfScope prof(ctx, stream, kid, flops, exec_flops);
-  hipLaunchKernelGGL((gemm_f16_nt_pipe_kernel<BM, BN, NST, LOADER, KS, BF, TC, NW>), dim3(ntiles * splits * ng), dim3(NW * 64), PT::LDS_BYTES,
+  hipLaunchKernelGGL((gemm_f16_nt_pipe_kernel<BM, BN, NST, LOADER, KS, BF, TC, NW, GRP>), dim3(ntiles * splits), dim3(NW * 64), PT::LDS_BYTES,
                      stream, p, splits);
   NERAF_HIP_CHECK(ctx, hipGetLastError());
   if (ctx && ctx->manifest) gemm_manifest(ctx, p, LOADER, splits, BM, BN, flops);
@@ -1446,14 +1467,24 @@ int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
   if (p.tile_n == 64 && (p.Mpad % 128) == 0 && !(kTile64 && LOADER == 1)) { bm = 128; bn = 64; }
   else if (!can128 || (p.Mpad / 128) * (p.Npad / 128) < cus) { bm = 64; bn = 64; }
   const int ng = p.ngroups > 1 ? p.ngroups : 1;
-  const int ntiles = (p.Mpad / bm) * (p.Npad / bn) * ng;
+  int ntiles = (p.Mpad / bm) * (p.Npad / bn);
+  bool uniform = true;
+  if (ng > 1) {
+    // a grouped launch gathers outputs that each under-fill the chip: 64x64 tiles, counted over the whole launch (below: 32x32 when even
+    // together they are few).  All 4-wave bodies add an output element's K-steps in the same order, so the shape changes no result.
+    bm = 64; bn = 64; ntiles = 0;
+    for (int g = 0; g < ng; ++g) {
+      ntiles += (round_up(p.grp[g].M, 64) / 64) * (round_up(p.grp[g].N, 64) / 64);
+      uniform = uniform && round_up(p.grp[g].M, 64) == p.Mpad && round_up(p.grp[g].N, 64) == p.Npad;
+    }
+  }
   // split-K: only with scratch, when the grid under-fills the chip and every slice keeps >= 4 K-steps
   int splits = 1;
   // implicit-GEMM convolutions on >= 64 tiles (the 4096-voxel layers) are split to TWO workgroups per CU: a lone 4-wave workgroup has
   // nothing to hide its LDS-DMA waits behind (16.1 -> 13.3 us per 27-tap convolution; on 32 tiles -- 512 voxels -- the extra slabs
   // cost the reducer what the GEMM gains: profiles/r05_splitk_oversubscription_ab.txt).  NERAF_SPLIT_OVERSUB=1 restores one per CU.
   static const int kOversub = [] { const char* e = getenv("NERAF_SPLIT_OVERSUB"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-  if (p.splitk_ws && ntiles * 2 <= cus && nk >= kSplitMinK) {
+  if (p.splitk_ws && uniform && ntiles * 2 <= cus && nk >= kSplitMinK) {      // groups of unequal shape have no common slab size
     splits = ((LOADER != 0 && ntiles >= 64) ? kOversub : 1) * cus / ntiles;
     if (splits > nk / 4) splits = nk / 4;
     if (splits > 128) splits = 128;
@@ -1477,7 +1508,11 @@ int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
   // (tools/small_gemm_bench.py), step -0.05 ms.  NERAF_TILE32 = largest 64x64-tile count that still takes the 32x32 form (0: off).
   static const int kTile32 = [] { const char* e = getenv("NERAF_TILE32"); return e ? atoi(e) : 128; }();
   if constexpr (LOADER == 0) {
-    if (kTile32 && ng == 1 && splits == 1 && bm == 64 && bn == 64 && ntiles <= kTile32 && !p.C16T)
+    if (ng > 1) {
+      if (kTile32 && splits == 1 && ntiles <= kTile32) return launch_pipe<32, 32, 4, LOADER, KS, BF, false, 4, true>(ctx, p, 1, stream);
+      return launch_pipe<64, 64, 4, LOADER, KS, BF, false, 4, true>(ctx, p, splits, stream);
+    }
+    if (kTile32 && splits == 1 && bm == 64 && bn == 64 && ntiles <= kTile32 && !p.C16T)
       return launch_pipe<32, 32, 4, LOADER, KS, BF>(ctx, p, 1, stream);
   }
   if (bm == 128 && bn == 128) return launch_pipe<128, 128, 2, LOADER, KS, BF>(ctx, p, splits, stream);
@@ -1596,13 +1631,33 @@ int launch_wgrad_grouped(neraf_ctx* ctx, const WgradItem* items, int n, const ha
 }
 
 
-int launch_gemm_f16(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
+int launch_gemm_f16(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
+  GemmParams p = p_in;
   if (p.K <= 0 || (p.K % BK) != 0) return neraf_fail(ctx, NERAF_EINVAL, "gemm: K must be a positive multiple of 64");
+  if (p.ngroups == 1) {               // a table of one: the ordinary launch of that group
+    const GemmParams::Group& G = p.grp[0];
+    p.A = G.A; p.B = G.B; p.C32 = G.C32; p.ldc32 = G.ldc32; p.M = G.M; p.N = G.N;
+    p.Mpad = round_up(G.M, 64); p.Npad = round_up(G.N, 64);
+    p.ngroups = 0;
+  }
+  if (p.ngroups > 1) {
+    if (p.ngroups > kMaxGemmGroups || p.conv.loader != 0 || p.C16 || p.C16T || p.colsum || p.colsumsq || p.lmask || p.add16)
+      return neraf_fail(ctx, NERAF_EINVAL, "gemm: grouped launches are plain GEMMs with fp32 results only");
+    for (int g = 0; g < p.ngroups; ++g) {
+      const GemmParams::Group& G = p.grp[g];
+      if (!G.A || !G.B || !G.C32 || G.M <= 0 || G.N <= 0)
+        return neraf_fail(ctx, NERAF_EINVAL, "gemm: every group needs operands, a result and positive M, N");
+    }
+    // the launch's own operands and extents stand for group 0 (the slab size of the equal-shape split-K form); padded extents a
+    // caller states must be group 0's, so that the two cannot drift apart
+    if ((p.Mpad && p.Mpad != round_up(p.grp[0].M, 64)) || (p.Npad && p.Npad != round_up(p.grp[0].N, 64)))
+      return neraf_fail(ctx, NERAF_EINVAL, "gemm: a grouped launch's Mpad / Npad, if given, are group 0's M / N rounded up to 64");
+    p.A = p.grp[0].A; p.B = p.grp[0].B; p.C32 = p.grp[0].C32; p.ldc32 = p.grp[0].ldc32;
+    p.M = p.grp[0].M; p.N = p.grp[0].N; p.Mpad = round_up(p.M, 64); p.Npad = round_up(p.N, 64);
+  }
   if ((p.Mpad % 64) != 0 || (p.Npad % 64) != 0 || p.M > p.Mpad || p.N > p.Npad || p.M <= 0 || p.N <= 0)
     return neraf_fail(ctx, NERAF_EINVAL, "gemm: Mpad/Npad must be multiples of 64 covering M/N");
   if (!p.stat_det && p.stat_rep > 1 && (p.stat_rep & (p.stat_rep - 1))) return neraf_fail(ctx, NERAF_EINVAL, "gemm: stat_rep must be a power of two");
-  if (p.ngroups > 1 && (p.ngroups > 6 || p.conv.loader != 0 || p.C16 || p.C16T || p.colsum || p.colsumsq || p.lmask || p.add16))
-    return neraf_fail(ctx, NERAF_EINVAL, "gemm: grouped launches are plain GEMMs with fp32 results only");
   if ((p.conv.loader == 0 && (p.lda % 8)) || (p.ldb % 8) || (p.C16 && (p.ldc16 % 8)) || (p.C16T && (p.ldc16t % 8)) ||
       (p.lmask && (p.ldmask % 4)))
     return neraf_fail(ctx, NERAF_EINVAL, "gemm: leading dimensions must keep 16-byte alignment");
@@ -1627,6 +1682,26 @@ extern "C" int neraf_gemm_f16(neraf_ctx* ctx, const void* A, int lda, const void
   p.A = (const half_t*)A; p.lda = lda; p.B = (const half_t*)B; p.ldb = ldb;
   p.M = M; p.N = N; p.K = K; p.Mpad = Mpad; p.Npad = Npad; p.alpha = alpha; p.bias = bias; p.act = act;
   p.C16 = (half_t*)C16; p.ldc16 = ldc16; p.C16T = (half_t*)C16T; p.ldc16t = ldc16t; p.C32 = C32; p.ldc32 = ldc32;
+  return launch_gemm_f16(ctx, p, (hipStream_t)stream);
+}
+
+// Up to six plain fp32-result GEMMs that share K, lda and ldb in ONE grid (the NAcF's narrow weight gradients, the radiance field's
+// five; the groups may differ in shape); exported for tests.  Padded extents are M and N rounded up to 64; one group is the ordinary single launch.
+extern "C" int neraf_gemm_f16_grouped(neraf_ctx* ctx, int ngroups, const void* const* A, const void* const* B, const int* M, const int* N,
+                                      float* const* C32, const int* ldc32, int lda, int ldb, int K, float alpha, const float* alpha_dev,
+                                      int c32_beta, void* splitk_ws, size_t splitk_bytes, neraf_stream_t stream) {
+  if (ngroups < 1 || ngroups > kMaxGemmGroups || !A || !B || !M || !N || !C32 || !ldc32)
+    return neraf_fail(ctx, NERAF_EINVAL, "gemm_f16_grouped: 1 to 6 groups");
+  GemmParams p{};
+  p.lda = lda; p.ldb = ldb; p.K = K; p.alpha = alpha; p.alpha_dev = alpha_dev; p.c32_beta = c32_beta;
+  p.splitk_ws = (float*)splitk_ws; p.splitk_ws_bytes = splitk_ws ? splitk_bytes : 0;
+  for (int g = 0; g < ngroups; ++g) {
+    if (M[g] <= 0 || N[g] <= 0) return neraf_fail(ctx, NERAF_EINVAL, "gemm_f16_grouped: M and N must be positive");
+    GemmParams::Group& G = p.grp[g];
+    G.A = (const half_t*)A[g]; G.B = (const half_t*)B[g]; G.C32 = C32[g]; G.M = M[g]; G.N = N[g]; G.ldc32 = ldc32[g];
+    if (!G.A || !G.B || !G.C32) return neraf_fail(ctx, NERAF_EINVAL, "gemm_f16_grouped: null operand or result");
+  }
+  p.ngroups = ngroups;
   return launch_gemm_f16(ctx, p, (hipStream_t)stream);
 }
 

@@ -68,7 +68,9 @@ struct WsLayout {
   size_t hd, hdT;          // dense input fp16 [Mpad][kdense_p], [kdense_p][Mpad]
   size_t h[5], hT[5];      // activations fp16 [Mpad][np], [np][Mpad]
   size_t bias0;            // fp32 [np0] effective layer-0 bias
-  size_t dz[2], dzT[2];    // backward ping-pong fp16 [Mpad][5120] / [5120+128][Mpad]
+  size_t dz[2];            // backward ping-pong fp16 [Mpad][5120]
+  size_t dzT[6];           // dz_l^T fp16 [np_l][Mpad], one slot per layer (heads: np_5 + 128 rows): every weight gradient is formed after the
+                           // dX chain, so each layer's transposed gradient lives to the end of the backward
   size_t colsum[6];        // fp32 [np]; deterministic mode: [Mpad / 32][np] slots (one per 32 rows, GemmParams::stat_det)
   size_t scale;            // fp32 [4]: {S, 1/S, amax bits, -} backward auto-scale
   size_t dfeat_part;       // deterministic mode: fp32 [64][n_feat] row-slice partials of d feat
@@ -99,10 +101,9 @@ WsLayout make_ws_layout(const neraf_nacf_desc* d, const Dims& D, int B, int trai
   if (training) {
     int maxw = 0;
     for (int l = 0; l < 6; ++l) maxw = D.np[l] > maxw ? D.np[l] : maxw;
-    for (int i = 0; i < 2; ++i) {
-      L.dz[i] = take(M * maxw * 2);
-      L.dzT[i] = take((size_t)(maxw + 128) * M * 2);
-    }
+    for (int i = 0; i < 2; ++i) L.dz[i] = take(M * maxw * 2);
+    // a head's 128-row-padded slice of dz_5^T may reach past np_5: + 128 rows
+    for (int l = 0; l < 6; ++l) L.dzT[l] = take((size_t)(D.np[l] + (l == 5 ? 128 : 0)) * M * 2);
     L.col_slots = neraf_deterministic() ? L.Mpad / 32 : 1;
     for (int l = 0; l < 6; ++l) L.colsum[l] = take((size_t)L.col_slots * D.np[l] * 4);
     L.scale = take(256);
@@ -678,11 +679,14 @@ extern "C" int neraf_nacf_fwd_dense(neraf_ctx* ctx, const neraf_nacf_desc* d, co
   return nacf_fwd_tail(ctx, d, D, PL, WL, P, ws, B, out, training, st);
 }
 
-// Backward through heads and trunk layers 4..1; leaves dz0 (+T) in ping-pong slot `*slot0` and
-// the column sums (bias grads) in ws colsum[l].
+// Backward through heads and trunk layers 4..1; leaves dz0 in ping-pong slot `*slot0`, dz0^T in dzT[0] and the column sums (bias
+// grads) in ws colsum[l].  The dX chain dz4 .. dz0 runs alone; no weight gradient feeds it, so they follow: dW1 (a full-chip GEMM)
+// in a launch of its own, then the narrow ones -- heads, layers 4, 3, 2 and, when `extra` is given, the caller's layer-0 gradient on
+// dz0^T -- as ONE grouped launch (K = Mpad, lda = ldb = Mpad for all of them).  Each of these alone leaves most CUs without a tile to
+// pull and pays a launch floor; together they are ~1200 64x64 tiles.
 static int nacf_bwd_body(neraf_ctx* ctx, const neraf_nacf_desc* d, const Dims& D, const PackLayout& PL, const WsLayout& WL,
                          const char* P, char* ws, int B, const float* out, const float* dout, float* const* grads,
-                         int* slot0, hipStream_t st) {
+                         const GemmParams::Group* extra, int* slot0, hipStream_t st) {
   const int M = WL.Mpad;
   // the six column-sum rows and the scale block are adjacent in the workspace (make_ws_layout): one fill
   neraf_zero_async(st, ws + WL.colsum[0], WL.scale + 256 - WL.colsum[0]);
@@ -702,52 +706,73 @@ static int nacf_bwd_body(neraf_ctx* ctx, const neraf_nacf_desc* d, const Dims& D
   const bool det = WL.col_slots > 1;          // deterministic mode: column sums in [Mpad / 32][np] slots, added in slot order on the way out
   outs.nslots = WL.col_slots;
   auto copy_out = [&](float* dst, const float* src, int n, int np) { seg_copy_add(outs, dst, src, n, n, np); };
+  // the narrow weight gradients, gathered behind the chain for the grouped launch (a launch holds kMaxGemmGroups: one for the RAF and
+  // SoundSpaces heads; with more heads the table is sent off whenever it is full)
+  GemmParams wg{};
+  wg.lda = M; wg.ldb = M; wg.K = M; wg.alpha = 1.f; wg.alpha_dev = inv_scale;
+  auto flush = [&]() -> int {
+    if (!wg.ngroups) return NERAF_OK;
+    const int e = launch_gemm_f16(ctx, wg, st);
+    wg.ngroups = 0;
+    return e;
+  };
+  auto add_group = [&](const GemmParams::Group& G) -> int {
+    if (wg.ngroups == kMaxGemmGroups) { if (int e = flush()) return e; }
+    wg.grp[wg.ngroups++] = G;
+    return NERAF_OK;
+  };
   int cur = 0;
   half_t* dz = (half_t*)(ws + WL.dz[cur]);
-  half_t* dzT = (half_t*)(ws + WL.dzT[cur]);
-  if (int e = cvt_pad_transpose(ctx, st, dout, out, scale, D.n[5], B, D.n[5], 1, dz, D.np[5], M, D.np[5], dzT, M, M, D.np[5] + 128,
+  half_t* dz5T = (half_t*)(ws + WL.dzT[5]);
+  if (int e = cvt_pad_transpose(ctx, st, dout, out, scale, D.n[5], B, D.n[5], 1, dz, D.np[5], M, D.np[5], dz5T, M, M, D.np[5] + 128,
                                 (float*)(ws + WL.colsum[5]), det ? D.np[5] : 0))
     return e;
-  for (int c = 0; c < d->C; ++c) {
-    // dWh_c [F, W] = dz5^T[cF:(c+1)F, :] . h4^T[W, :]^T
-    GemmParams g{};
-    g.A = dzT + (size_t)c * d->F * M; g.lda = M;
-    g.B = (const half_t*)(ws + WL.hT[4]); g.ldb = M;
-    g.M = d->F; g.N = D.n[4]; g.K = M; g.Mpad = round_up(d->F, 128); g.Npad = D.np[4]; g.alpha = 1.f;
-    g.alpha_dev = inv_scale;
-    g.C32 = grads[2 * (5 + c)]; g.ldc32 = D.n[4];
-    if (int e = launch_gemm_f16(ctx, g, st)) return e;
+  for (int c = 0; c < d->C; ++c)
     copy_out(grads[2 * (5 + c) + 1], (const float*)(ws + WL.colsum[5]) + (size_t)c * d->F, d->F, D.np[5]);
-  }
   for (int l = 5; l >= 1; --l) {
     // dz_{l-1} = (dz_l . W_l) * leaky'(h_{l-1})   [Mpad, np_{l-1}]
     const int nxt = cur ^ 1;
-    half_t* dzn = (half_t*)(ws + WL.dz[nxt]);
-    half_t* dznT = (half_t*)(ws + WL.dzT[nxt]);
     GemmParams g{};
     g.A = (const half_t*)(ws + WL.dz[cur]); g.lda = D.np[l];
     g.B = (const half_t*)(P + PL.wt[l]); g.ldb = D.np[l];
     g.M = B; g.N = D.n[l - 1]; g.K = D.np[l]; g.Mpad = M; g.Npad = D.np[l - 1]; g.alpha = 1.f;
     g.lmask = (const half_t*)(ws + WL.h[l - 1]); g.ldmask = D.np[l - 1]; g.mask_slope = 0.1f;
-    g.C16 = dzn; g.ldc16 = D.np[l - 1];
-    g.C16T = dznT; g.ldc16t = M;
+    g.C16 = (half_t*)(ws + WL.dz[nxt]); g.ldc16 = D.np[l - 1];
+    g.C16T = (half_t*)(ws + WL.dzT[l - 1]); g.ldc16t = M;
     g.colsum = (float*)(ws + WL.colsum[l - 1]);
     if (det) { g.stat_det = 1; g.stat_stride = D.np[l - 1]; }
     if (int e = launch_gemm_f16(ctx, g, st)) return e;
     cur = nxt;
-    if (l - 1 >= 1) {
-      // dW_{l-1} [n_{l-1}, k_{l-1}] = dz_{l-1}^T . h_{l-2}^T^T
-      GemmParams w{};
-      w.A = dznT; w.lda = M;
-      w.B = (const half_t*)(ws + WL.hT[l - 2]); w.ldb = M;
-      w.M = D.n[l - 1]; w.N = D.k[l - 1]; w.K = M; w.Mpad = D.np[l - 1]; w.Npad = D.kp[l - 1]; w.alpha = 1.f;
-      w.alpha_dev = inv_scale;
-      w.C32 = grads[2 * (l - 1)]; w.ldc32 = D.k[l - 1];
-      if (int e = launch_gemm_f16(ctx, w, st)) return e;
-      copy_out(grads[2 * (l - 1) + 1], (const float*)(ws + WL.colsum[l - 1]), D.n[l - 1], D.np[l - 1]);
-    }
+    copy_out(grads[2 * (l - 1) + 1], (const float*)(ws + WL.colsum[l - 1]), D.n[l - 1], D.np[l - 1]);
   }
-  copy_out(grads[1], (const float*)(ws + WL.colsum[0]), D.n[0], D.np[0]);
+  {
+    // dW_1 [2048, 5096] = dz_1^T . h_0^T^T fills the chip by itself
+    GemmParams w{};
+    w.A = (const half_t*)(ws + WL.dzT[1]); w.lda = M;
+    w.B = (const half_t*)(ws + WL.hT[0]); w.ldb = M;
+    w.M = D.n[1]; w.N = D.k[1]; w.K = M; w.Mpad = D.np[1]; w.Npad = D.kp[1]; w.alpha = 1.f;
+    w.alpha_dev = inv_scale;
+    w.C32 = grads[2]; w.ldc32 = D.k[1];
+    if (int e = launch_gemm_f16(ctx, w, st)) return e;
+  }
+  for (int c = 0; c < d->C; ++c) {
+    // dWh_c [F, W] = dz5^T[cF:(c+1)F, :] . h4^T[W, :]^T
+    GemmParams::Group G{};
+    G.A = dz5T + (size_t)c * d->F * M; G.B = (const half_t*)(ws + WL.hT[4]);
+    G.M = d->F; G.N = D.n[4];
+    G.C32 = grads[2 * (5 + c)]; G.ldc32 = D.n[4];
+    if (int e = add_group(G)) return e;
+  }
+  for (int l = 4; l >= 2; --l) {
+    // dW_l [n_l, k_l] = dz_l^T . h_{l-1}^T^T
+    GemmParams::Group G{};
+    G.A = (const half_t*)(ws + WL.dzT[l]); G.B = (const half_t*)(ws + WL.hT[l - 1]);
+    G.M = D.n[l]; G.N = D.k[l];
+    G.C32 = grads[2 * l]; G.ldc32 = D.k[l];
+    if (int e = add_group(G)) return e;
+  }
+  if (extra) { if (int e = add_group(*extra)) return e; }
+  if (int e = flush()) return e;
   hipLaunchKernelGGL(seg_copy_kernel, dim3(outs.begin[outs.n]), dim3(256), 0, st, outs);
   NERAF_HIP_CHECK(ctx, hipGetLastError());
   *slot0 = cur;
@@ -766,16 +791,12 @@ extern "C" int neraf_nacf_bwd(neraf_ctx* ctx, const neraf_nacf_desc* d, const vo
   const char* P = (const char*)packed;
   char* ws = (char*)workspace;
   int s0 = 0;
-  if (int e = nacf_bwd_body(ctx, d, D, PL, WL, P, ws, B, out, dout, grads, &s0, st)) return e;
-  const int M = WL.Mpad;
-  // dW0[:, n_feat:] = dz0^T . q^T^T   (N = 163, padded 256)
-  GemmParams g{};
-  g.A = (const half_t*)(ws + WL.dzT[s0]); g.lda = M;
-  g.B = (const half_t*)(ws + WL.qT); g.ldb = M;
-  g.M = D.n[0]; g.N = D.k[0]; g.K = M; g.Mpad = D.np[0]; g.Npad = QT_ROWS; g.alpha = 1.f;
-  g.alpha_dev = (const float*)(ws + WL.scale) + 1;
-  g.C32 = grads[0] + d->n_feat; g.ldc32 = D.kdense;
-  if (int e = launch_gemm_f16(ctx, g, st)) return e;
+  // dW0[:, n_feat:] = dz0^T . q^T^T   (N = 163: the 64-wide tiles walk 192 of q^T's 256 rows): a member of the grouped launch
+  GemmParams::Group q{};
+  q.A = (const half_t*)(ws + WL.dzT[0]); q.B = (const half_t*)(ws + WL.qT);
+  q.M = D.n[0]; q.N = D.k[0];
+  q.C32 = grads[0] + d->n_feat; q.ldc32 = D.kdense;
+  if (int e = nacf_bwd_body(ctx, d, D, PL, WL, P, ws, B, out, dout, grads, &q, &s0, st)) return e;
   const float* db0 = grads[1];   // un-scaled layer-0 bias gradient
   if (d->n_feat > 0) {
     hipLaunchKernelGGL(outer_kernel, dim3((d->n_feat + 255) / 256, D.n[0]), dim3(256), 0, st, db0, feat, D.n[0], d->n_feat,
@@ -804,10 +825,10 @@ extern "C" int neraf_nacf_bwd_dense(neraf_ctx* ctx, const neraf_nacf_desc* d, co
   const char* P = (const char*)packed;
   char* ws = (char*)workspace;
   int s0 = 0;
-  if (int e = nacf_bwd_body(ctx, d, D, PL, WL, P, ws, B, out, dout, grads, &s0, st)) return e;
+  if (int e = nacf_bwd_body(ctx, d, D, PL, WL, P, ws, B, out, dout, grads, nullptr, &s0, st)) return e;
   const int M = WL.Mpad;
   GemmParams g{};
-  g.A = (const half_t*)(ws + WL.dzT[s0]); g.lda = M;
+  g.A = (const half_t*)(ws + WL.dzT[0]); g.lda = M;
   g.B = (const half_t*)(ws + WL.hdT); g.ldb = M;
   g.M = D.n[0]; g.N = D.kdense; g.K = M; g.Mpad = D.np[0]; g.Npad = D.kdense_p; g.alpha = 1.f;
   g.alpha_dev = (const float*)(ws + WL.scale) + 1;

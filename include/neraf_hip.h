@@ -95,6 +95,20 @@ int neraf_gemm_f16_grouped(neraf_ctx* ctx, int ngroups, const void* const* A, co
                            float* const* C32, const int* ldc32, int lda, int ldb, int K, float alpha, const float* alpha_dev,
                            int c32_beta, void* splitk_ws, size_t splitk_bytes, neraf_stream_t stream);
 
+/* Plain fp16 GEMM with the epilogue the 1x1x1 convolutions of ResNet3D layer 1 use -- alpha, optional fp16 add16 [Mpad][>= N],
+ * C16, column sums / sums of squares (replicated stat_rep times stat_stride floats apart and added atomically, or with stat_det
+ * stored into one slot per 32 result rows) -- and a choice of body (exported for tests and tools/stream_gemm_bench.py):
+ * body 0 = the dispatcher's choice; 1 = the streaming body (B resident in LDS, A streamed in 64-row blocks), NERAF_EINVAL with
+ * nothing written unless N = Npad in {64, 128, 256}, K in {64, 128, 256}, N * K <= 16384 and bias, C16T and C32 are null;
+ * 2 = never the streaming body.  max_workgroups > 0 caps the streaming grid (0 = sized from the CU count).  C16 is bit-identical
+ * under every body; the statistics agree to rounding.  With stat_det the streaming body stores a workgroup's sums into the slot
+ * of its first row block and leaves every other slot at the caller's zero; the dispatcher (body 0) keeps a GEMM with
+ * deterministic statistics on the tile bodies, whose slot sums a deterministic run has always had. */
+int neraf_gemm_f16_stream(neraf_ctx* ctx, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int Mpad, int Npad,
+                          float alpha, const float* bias, const void* add16, int ldadd, void* C16, int ldc16, void* C16T,
+                          int ldc16t, float* C32, int ldc32, float* colsum, float* colsumsq, int stat_rep, int stat_stride,
+                          int stat_det, int body, int max_workgroups, neraf_stream_t stream);
+
 /* The same contraction with bfloat16 operands / 16-bit results (used by the deep gradient chains). */
 int neraf_gemm_bf16(neraf_ctx* ctx, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
                     int Mpad, int Npad, float alpha, const float* bias, int act,

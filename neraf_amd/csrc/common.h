@@ -240,6 +240,9 @@ struct GemmParams {
   // it); the tile shape is chosen from the launch's total tile count, tile_begin (set by the launcher) is the group's first tile in
   // that shape, and a workgroup finds its group by walking this table.  Only groups of equal padded shape are split along K.  Used
   // for the small-output weight gradients, each of which alone under-fills the chip and pays a launch floor.
+  // streaming body for short-K plain GEMMs (gemm_f16_nt_stream_kernel), private to neraf_gemm_f16_stream: stream_body 0 = the
+  // dispatcher's choice, 1 = streaming or NERAF_EINVAL, 2 = never streaming; stream_max_wg > 0 caps its grid (0 = from the CU count)
+  int stream_body, stream_max_wg;
   int ngroups;
   struct Group { const half_t* A; const half_t* B; float* C32; int M, N, ldc32; int tile_begin; } grp[6];
 };

@@ -18,7 +18,8 @@
 // zero page for padding).  Under-filled grids (few tiles, long K) are split along K into fp32 partial slabs that
 // a second kernel reduces and finishes.
 // Bodies in this file: gemm_f16_nt_pipe_kernel (4 waves; 128x128 / 128x64 / 64x64 tiles, plain or implicit-conv loader),
-// gemm_f16_nt_wide_kernel (8 waves, ping-pong K loop; 256x160, 256x128, 128x128 tiles of plain GEMMs), the bf16 "TN" weight-gradient
+// gemm_f16_nt_wide_kernel (8 waves, ping-pong K loop; 256x160, 256x128, 128x128 tiles of plain GEMMs), gemm_f16_nt_stream_kernel (B resident
+// in LDS, A streamed in 64-row blocks: the short-K plain GEMMs over 32768 rows), the bf16 "TN" weight-gradient
 // kernels wgrad_grouped_tn_kernel / wgrad_wide_tn_kernel over all convolutions of a backward pass, and their reducers.
 #include "common.h"
 #include <stdlib.h>
@@ -836,7 +837,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p, int sp
 
 // manifest records (neraf_manifest_enable) of one GEMM launch and, with split-K, of its reducer: operands once (an implicit-GEMM
 // convolution reads its source tensor once, not once per tap), results once; the K-split slabs where they are written and read
-static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int splits, int bm, int bn, double flops, bool wide = false) {
+static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int splits, int bm, int bn, double flops, bool wide = false, bool stream = false) {
   double out_elems = (double)p.M * p.N;
   double rA = loader == 0 ? (double)p.M * p.K * 2.0 : (double)p.conv.din * p.conv.din * p.conv.din * p.conv.cin * 2.0;
   double rB = (double)p.N * p.K * 2.0;
@@ -853,7 +854,8 @@ static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int s
   if (ng > 1)
     snprintf(nm, sizeof(nm), "gemm_f16_nt_pipe_kernel<%d, %d | plain, %d groups, %.0f results K=%d%s", bm, bn, ng, out_elems, p.K, splits > 1 ? " splitK" : "");
   else
-    snprintf(nm, sizeof(nm), "%s<%d, %d | %s M=%d N=%d K=%d%s", wide ? "gemm_f16_nt_wide_kernel" : "gemm_f16_nt_pipe_kernel", bm, bn,
+    snprintf(nm, sizeof(nm), "%s<%d, %d | %s M=%d N=%d K=%d%s",      // the streaming body's template arguments are <N, K, ...>
+             stream ? "gemm_f16_nt_stream_kernel" : (wide ? "gemm_f16_nt_wide_kernel" : "gemm_f16_nt_pipe_kernel"), bm, bn,
              loader == 0 ? "plain" : (p.conv.tflip ? "dgrad" : "conv"), p.M, p.N, p.K, splits > 1 ? " splitK" : "");
   if (splits > 1) {
     neraf_node(ctx, nm, flops, rA + rB, slabs);
@@ -925,6 +927,229 @@ int launch_wide(neraf_ctx* ctx, const GemmParams& p, int splits, hipStream_t str
     NERAF_HIP_CHECK(ctx, hipGetLastError());
   }
   return NERAF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Streaming body for plain fp16 GEMMs with a short K and a narrow N (the 1x1x1 convolutions of ResNet3D layer 1 and their dgrads:
+// M = 32768, N x K = 256 x 64, 64 x 256, 64 x 64): 1 GFLOP against 20-40 MB, so the launch is a memory stream and the tile bodies
+// above -- one tile per CU, operand round trip, MFMAs, result image, atomics, nothing overlapping -- spend it in prologue and epilogue.
+// Here B (N * K <= 16384 elements, 32 KiB) is loaded ONCE per workgroup into LDS, rows K halfs apart with the 16-byte chunk index
+// XORed by the row (conflict-free ds_read_b128 fragments), and stays; a workgroup holds at most 128 of its columns, so N = 256 runs
+// as CS = 2 column slices, workgroup (row group rg, slice c), the two slices of a row group on the same XCD (one L2 serves A's second
+// reading).  A is walked in 64-row blocks by static assignment: the eight waves are two walkers of four waves, walker v = 2 rg + g
+// takes blocks v, v + nv, v + 2 nv, ... (nv walkers in the launch; no dequeue, no synchronisation between workgroups, none between
+// waves inside the walk); wave w of a walker owns rows [16 w, 16 w + 16) of the block across the workgroup's columns:
+//   * its A operand never passes LDS: lane (row = lane & 15, q = lane >> 4) loads the 16 bytes A[row][32 kb + 8 q ..] per 32-deep K
+//     block kb, which IS that lane's 16x16x32 fragment; the next block's fragments are requested before this block's MFMAs
+//   * accumulation is that of the 4-wave bodies: one accumulator per element, K blocks of 32 in ascending order, the same MFMA with
+//     the same operand order and k-to-lane assignment, so C16 is bit-identical to theirs
+//   * results leave through a wave-private LDS image of 16 rows x 64 columns as 16-byte stores of whole 128-byte row segments
+//   * column sums stay in registers over all the blocks of the walk; at the end one workgroup-wide reduction and ONE atomic per
+//     column (replica rg & (stat_rep - 1)) or, with stat_det, one plain store into the slot of the workgroup's first block (its first
+//     row / 32 = 4 rg; every other slot keeps the caller's zero).  What the memory system serialises is the number of atomics per
+//     column, rows / (rows per workgroup): 128 rows of every block pair per workgroup, 256 with two slices, is the tile bodies' count.
+//     The grid is a function of the shape and the CU count alone, so the deterministic sums are bit-reproducible; their order
+//     differs from the tile bodies' (DESIGN.md section 7).
+// Epilogue: alpha (scalar), add16, C16 (any ldc16), colsum / colsumsq.  Rows in [M, Mpad) are stored as zeros and add nothing to
+// the sums; nothing at or beyond row Mpad is touched.  Static LDS <= 50 KiB: no function attribute, safe in captured graphs.
+constexpr int kStreamRows = 64;
+constexpr int stream_slices(int n) { return n > 128 ? n / 128 : 1; }
+
+// sum over the 16 lanes that share lane >> 4 (every one of them receives it): two quad permutes, then the row's half mirror and mirror
+__device__ __forceinline__ float row16_sum(float x) {
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // quad_perm [1, 0, 3, 2]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // quad_perm [2, 3, 0, 1]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));   // row_half_mirror
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // row_mirror
+  return x;
+}
+
+template <int N, int K, bool STATS>
+__global__ __launch_bounds__(512) void gemm_f16_nt_stream_kernel(GemmParams p, int nblocks, int nrg) {
+  constexpr int R = kStreamRows, KB = K / 32;
+  constexpr int CS = stream_slices(N), NW = N / CS, FNW = NW / 16;   // column slices of the launch; columns / fragments of a workgroup
+  constexpr int CPRB = K / 8, SWZ = (CPRB - 1) & 15;            // 16-byte chunks per B row; row bits XORed into the chunk index
+  constexpr int BCH = NW * CPRB / 512;                          // B chunks a thread stages
+  constexpr int IC = 64, NPASS = NW / IC, FNP = IC / 16, IMG_LD = IC + 8, CPR = IC / 8, IMG_WAVE = 16 * IMG_LD * 2;
+  static_assert(N * K <= 16384 && N % 64 == 0 && K % 64 == 0 && NW <= 128 && BCH >= 1, "B must fit 32 KiB of LDS");
+  static_assert(8 * 2 * NW * 4 <= 8 * IMG_WAVE, "the statistics' reduction re-uses the result images");
+  __shared__ __attribute__((aligned(16))) char bs[NW * K * 2];
+  __shared__ __attribute__((aligned(16))) char img_all[8 * IMG_WAVE];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = wave >> 2, w4 = wave & 3;                        // walker of the workgroup, wave of the walker
+  const int frow = lane & 15, fq = lane >> 4;
+  // workgroup -> (row group, column slice); with whole groups of 8 row groups the slices of a row group share blockIdx & 7, the XCD
+  int rg, cs;
+  if (CS > 1 && (nrg & 7) == 0) { const int q = blockIdx.x >> 3; cs = q % CS; rg = (q / CS) * 8 + (blockIdx.x & 7); }
+  else { rg = blockIdx.x / CS; cs = blockIdx.x - rg * CS; }
+  const int n_w0 = cs * NW;
+  const int nv = 2 * nrg;
+
+  auto load_a = [&](int blk, half8 (&xa)[KB]) {
+    const half_t* src = p.A + (size_t)(blk * R + w4 * 16 + frow) * p.lda + fq * 8;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) xa[kb] = *reinterpret_cast<const half8*>(src + kb * 32);
+  };
+
+  int b = 2 * rg + g;                                            // the second walker of the last row group may own no block
+  half8 xa[KB], xn[KB];
+  {
+    uint4 bv[BCH];
+#pragma unroll
+    for (int i = 0; i < BCH; ++i) {
+      const int c = i * 512 + tid, row = c / CPRB, ch = c % CPRB;
+      bv[i] = *reinterpret_cast<const uint4*>(p.B + (size_t)(n_w0 + row) * p.ldb + ch * 8);
+    }
+    if (b < nblocks) load_a(b, xa);
+#pragma unroll
+    for (int i = 0; i < BCH; ++i) {
+      const int c = i * 512 + tid, row = c / CPRB, ch = c % CPRB;
+      *reinterpret_cast<uint4*>(bs + row * (K * 2) + ((ch ^ (row & SWZ)) * 16)) = bv[i];
+    }
+  }
+  __syncthreads();
+
+  const float alpha = p.alpha;
+  half_t* im = reinterpret_cast<half_t*>(img_all + wave * IMG_WAVE);
+  const char* b_lane = bs + frow * (K * 2);
+  f32x4 s[STATS ? FNW : 1], s2[STATS ? FNW : 1];
+#pragma unroll
+  for (int j = 0; j < (STATS ? FNW : 1); ++j) s[j] = s2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (; b < nblocks; b += nv) {
+    const int bnext = b + nv;
+    if (bnext < nblocks) load_a(bnext, xn);
+
+    f32x4 acc[FNW];
+#pragma unroll
+    for (int j = 0; j < FNW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const int coff = ((kb * 4 + fq) ^ (frow & SWZ)) * 16;
+#pragma unroll
+      for (int j = 0; j < FNW; ++j) {
+        const half8 wb = *reinterpret_cast<const half8*>(b_lane + j * 16 * (K * 2) + coff);
+        // D[r = n][c = m], as in the tile bodies: W fragment is the MFMA "A" operand, X fragment the "B" operand
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb, xa[kb], acc[j], 0, 0, 0);
+      }
+    }
+
+    // lane holds, for fragment j: m = row0 + (lane & 15), n = n_w0 + j * 16 + (lane >> 4) * 4 + r
+    const int row0 = b * R + w4 * 16;
+    const int m = row0 + frow;
+    const bool live = m < p.M;
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+      half4 ad[FNP];
+      if (p.add16) {
+#pragma unroll
+        for (int j = 0; j < FNP; ++j)
+          ad[j] = *reinterpret_cast<const half4*>(p.add16 + (size_t)m * p.ldadd + n_w0 + pass * IC + j * 16 + fq * 4);
+      }
+#pragma unroll
+      for (int j = 0; j < FNP; ++j) {
+        const int jj = pass * FNP + j;
+        f32x4 v = acc[jj] * alpha;
+        if (p.add16) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += (float)ad[j][r];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (!live) v[r] = 0.f;
+        if constexpr (STATS) { s[jj] += v; s2[jj] += v * v; }
+        half4 h;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[r] = (half_t)v[r];
+        *reinterpret_cast<half4*>(im + frow * IMG_LD + j * 16 + fq * 4) = h;
+      }
+      // the image is this wave's own and the LDS serves a wave's accesses in order: no barrier, only the writes' completion
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int it = 0; it < 16 * CPR / 64; ++it) {
+        const int idx = it * 64 + lane, row = idx / CPR, ch = idx - row * CPR;
+        const uint4 d = *reinterpret_cast<const uint4*>(im + row * IMG_LD + ch * 8);
+        *reinterpret_cast<uint4*>(p.C16 + (size_t)(row0 + row) * p.ldc16 + n_w0 + pass * IC + ch * 8) = d;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the reads have returned before the next pass / block rewrites the image
+    }
+    if (bnext < nblocks) {
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) xa[kb] = xn[kb];
+    }
+  }
+
+  if constexpr (STATS) {
+    // column sums of the walks: over the 16 lanes (lane & 15) sharing a column in registers, over the eight waves through LDS in a
+    // fixed order, then one atomic (or, deterministic, one plain store) per column
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(img_all);      // [wave][sum | sumsq][NW]
+#pragma unroll
+    for (int j = 0; j < FNW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float x = row16_sum(s[j][r]), y = row16_sum(s2[j][r]);
+        if (frow == 0) {
+          const int col = j * 16 + fq * 4 + r;
+          red[(wave * 2 + 0) * NW + col] = x;
+          red[(wave * 2 + 1) * NW + col] = y;
+        }
+      }
+    __syncthreads();
+    if (tid < 2 * NW) {
+      const int which = tid / NW, col = tid - which * NW;
+      float v = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) v += red[(w * 2 + which) * NW + col];
+      float* dst = which ? p.colsumsq : p.colsum;
+      if (dst) {
+        if (p.stat_det) dst[(size_t)((2 * rg * R) >> 5) * p.stat_stride + n_w0 + col] = v;
+        else atomicAdd(dst + (p.stat_rep > 1 ? (rg & (p.stat_rep - 1)) * p.stat_stride : 0) + n_w0 + col, v);
+      }
+    }
+  }
+}
+
+// the shapes and epilogues the streaming body serves (everything ResNet3D layer 1 asks of a plain GEMM)
+static bool stream_qualifies(const GemmParams& p) {
+  const bool nk = (p.N == 64 || p.N == 128 || p.N == 256) && (p.K == 64 || p.K == 128 || p.K == 256) && p.N * p.K <= 16384;
+  return nk && p.Npad == p.N && p.conv.loader == 0 && p.ngroups <= 1 && !p.bf16 && (p.Mpad % kStreamRows) == 0 && p.C16 &&
+         !p.bias && !p.act && !p.lmask && !p.C16T && !p.C32 && !p.alpha_dev && !p.bnb_x && !p.bnb_mask &&
+         (!p.add16 || (p.ldadd % 4) == 0);
+}
+
+template <int N, int K>
+int launch_stream_nk(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
+  const int nblocks = p.Mpad / kStreamRows;
+  // one workgroup of eight waves (two walkers) per CU and column slice of it: row groups = CUs / slices, never more than block pairs
+  constexpr int CS = stream_slices(N);
+  int nrg = (ctx ? ctx->num_cus : 256) / CS;
+  if (p.stream_max_wg > 0 && nrg > p.stream_max_wg / CS) nrg = p.stream_max_wg / CS;
+  if (nrg > (nblocks + 1) / 2) nrg = (nblocks + 1) / 2;
+  if (nrg < 1) nrg = 1;
+  const int grid = nrg * CS;
+  const double flops = p.alg_flops > 0.0 ? p.alg_flops : 2.0 * p.M * p.N * p.K;
+  // accounted to the family the shape ran in before: 64-wide outputs to the 128x64 tile, the others to the wide body
+  ProfScope prof(ctx, stream, N == 64 ? PROF_GEMM12864 : PROF_GEMM_WIDE, flops, 2.0 * p.M * p.N * p.K);
+  if (p.colsum || p.colsumsq) hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, true>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
+  else hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, false>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
+  NERAF_HIP_CHECK(ctx, hipGetLastError());
+  if (ctx && ctx->manifest) gemm_manifest(ctx, p, 0, 1, N, K, flops, false, true);
+  return NERAF_OK;
+}
+
+int launch_stream(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
+  switch (p.N * 1000 + p.K) {
+    case 64064: return launch_stream_nk<64, 64>(ctx, p, stream);
+    case 64128: return launch_stream_nk<64, 128>(ctx, p, stream);
+    case 64256: return launch_stream_nk<64, 256>(ctx, p, stream);
+    case 128064: return launch_stream_nk<128, 64>(ctx, p, stream);
+    case 128128: return launch_stream_nk<128, 128>(ctx, p, stream);
+    case 256064: return launch_stream_nk<256, 64>(ctx, p, stream);
+  }
+  return neraf_fail(ctx, NERAF_EINVAL, "gemm: shape outside the streaming body's");
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1441,6 +1666,8 @@ static const int kSplitMinK = [] { const char* e = getenv("NERAF_SPLIT_MIN_K"); 
 // NERAF_CONV_WAVES=8: the implicit-GEMM convolutions' 64x64 tiles on 8 waves per workgroup (gemm_f16_nt_pipe_kernel NW)
 static bool conv_waves8() { static const bool v = [] { const char* e = getenv("NERAF_CONV_WAVES"); return e && atoi(e) == 8; }(); return v; }
 
+constexpr int kStreamMinM = 32768;     // rows (Mpad) from which a qualifying plain GEMM takes the streaming body
+
 template <int LOADER, int KS, bool BF>
 int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
   GemmParams p = p_in;
@@ -1455,6 +1682,19 @@ int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
     p.conv.tclass = 1;
     if constexpr (LOADER == 1) { if (conv_waves8()) return launch_pipe<64, 64, 4, LOADER, KS, BF, true, 8>(ctx, p, 1, stream); }
     return launch_pipe<64, 64, 4, LOADER, KS, BF, LOADER == 1>(ctx, p, 1, stream);
+  }
+  // short-K, narrow-N plain GEMMs over many rows are memory streams: the streaming body (gemm_f16_nt_stream_kernel) from kStreamMinM
+  // rows on -- ResNet3D layer 1 (32768 voxels), the only size measured (profiles/gemm_stream_ab.txt); the 4096- and 512-voxel
+  // layers and the NAcF keep their bodies.  stream_body (neraf_gemm_f16_stream) forces it on (1) or off (2).
+  // Deterministic statistics (stat_det) stay on the tile bodies unless forced: the streaming body's slot sums are reproducible but
+  // add the rows in another order, and the encoder's ReLU gates turn that last bit into different gradients -- a deterministic run
+  // must give the bits it gave before (bench.py --dump-outputs).  GEMMs without statistics stream in that mode too: C16 is the same.
+  if (p.stream_body == 1 && !(LOADER == 0 && !BF && stream_qualifies(p)))
+    return neraf_fail(ctx, NERAF_EINVAL, "gemm: shape or epilogue outside the streaming body's");
+  if constexpr (LOADER == 0 && !BF) {
+    const bool det_stats = p.stat_det && (p.colsum || p.colsumsq);
+    if (p.stream_body != 2 && stream_qualifies(p) && (p.stream_body == 1 || (p.Mpad >= kStreamMinM && !det_stats)))
+      return launch_stream(ctx, p, stream);
   }
   const int nk = p.K / BK;
   // tile choice: 128x128 when it fills the chip; 128x64 for 64-wide outputs; otherwise 64x64 (4x the workgroups)
@@ -1702,6 +1942,25 @@ extern "C" int neraf_gemm_f16_grouped(neraf_ctx* ctx, int ngroups, const void* c
     if (!G.A || !G.B || !G.C32) return neraf_fail(ctx, NERAF_EINVAL, "gemm_f16_grouped: null operand or result");
   }
   p.ngroups = ngroups;
+  return launch_gemm_f16(ctx, p, (hipStream_t)stream);
+}
+
+// Plain fp16 GEMM with the epilogue ResNet3D layer 1 uses and a choice of body (exported for tests and the A/B microbenchmark):
+// body 0 = the dispatcher's choice, 1 = the streaming body or NERAF_EINVAL where the parameters do not qualify, 2 = never the
+// streaming body.  max_workgroups > 0 caps the streaming grid, so that a small matrix makes every workgroup walk many row blocks.
+extern "C" int neraf_gemm_f16_stream(neraf_ctx* ctx, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int Mpad, int Npad,
+                                     float alpha, const float* bias, const void* add16, int ldadd, void* C16, int ldc16, void* C16T,
+                                     int ldc16t, float* C32, int ldc32, float* colsum, float* colsumsq, int stat_rep, int stat_stride,
+                                     int stat_det, int body, int max_workgroups, neraf_stream_t stream) {
+  if (body < 0 || body > 2 || max_workgroups < 0) return neraf_fail(ctx, NERAF_EINVAL, "gemm_f16_stream: body 0..2, max_workgroups >= 0");
+  GemmParams p{};
+  p.A = (const half_t*)A; p.lda = lda; p.B = (const half_t*)B; p.ldb = ldb;
+  p.M = M; p.N = N; p.K = K; p.Mpad = Mpad; p.Npad = Npad; p.alpha = alpha; p.bias = bias;
+  p.add16 = (const half_t*)add16; p.ldadd = ldadd;
+  p.C16 = (half_t*)C16; p.ldc16 = ldc16; p.C16T = (half_t*)C16T; p.ldc16t = ldc16t; p.C32 = C32; p.ldc32 = ldc32;
+  p.colsum = colsum; p.colsumsq = colsumsq; p.stat_rep = stat_rep; p.stat_stride = stat_stride; p.stat_det = stat_det;
+  p.tile_n = N == 64 ? 64 : 0;          // as the ResNet3D callers ask for 64-wide outputs
+  p.stream_body = body; p.stream_max_wg = max_workgroups;
   return launch_gemm_f16(ctx, p, (hipStream_t)stream);
 }
 

@@ -99,7 +99,7 @@ int neraf_gemm_f16_grouped(neraf_ctx* ctx, int ngroups, const void* const* A, co
  * C16, column sums / sums of squares (replicated stat_rep times stat_stride floats apart and added atomically, or with stat_det
  * stored into one slot per 32 result rows) -- and a choice of body (exported for tests and tools/stream_gemm_bench.py):
  * body 0 = the dispatcher's choice; 1 = the streaming body (B resident in LDS, A streamed in 64-row blocks), NERAF_EINVAL with
- * nothing written unless N = Npad in {64, 128, 256}, K in {64, 128, 256}, N * K <= 16384 and bias, C16T and C32 are null;
+ * nothing written unless N = Npad in {64, 128, 256}, K in {64, 128, 256}, N * K <= 32768 (a workgroup holds a slice of B of at most 32 KiB) and bias, C16T and C32 are null;
  * 2 = never the streaming body.  max_workgroups > 0 caps the streaming grid (0 = sized from the CU count).  C16 is bit-identical
  * under every body; the statistics agree to rounding.  With stat_det the streaming body stores a workgroup's sums into the slot
  * of its first row block and leaves every other slot at the caller's zero; the dispatcher (body 0) keeps a GEMM with
@@ -575,6 +575,23 @@ int neraf_gather_f16(neraf_ctx* ctx, const float* const* src, const long long* s
  * the stem max-pool (tap = (dz+1)*9 + (dy+1)*3 + (dx+1), 255 = window maximum not > 0; training forward only); 5: fp16 pre-BN
  * output of convolution `index`; 6: fp32 [2][cols] batch mean / biased variance of BatchNorm `index`. */
 int neraf_resnet3d_debug_locate(const neraf_resnet3d_desc* d, int kind, int index, size_t* offset, int* rows, int* cols);
+
+/* Test aids: ONE element-wise pass of the encoder on caller tensors (fp16 channels-last [rows][C]; not part of the product path).
+ * bn5 = HOST array of five device pointers {stats, gamma, beta, running_mean, running_var}: stats fp32 [rep][2][Cpad] (column sums and
+ * sums of squares, Cpad = C rounded up to 128, replicas 1024 floats apart, rep 1..16) selects the batch statistics over M rows,
+ * stats = NULL the running ones.
+ *   neraf_debug_bn_apply:    out [Mpad][C] = [relu]( bn(x) [+ res | + bn_r(xr)] ), rows >= M zero; Mpad a multiple of 128.  form 0 = the
+ *                            small-launch kernel, 1 = the tile kernel of the large tensors (C a multiple of 64).  fin_w / fin_w_r
+ *                            (may be NULL): fp32 [2][Cpad] mean and biased variance as the pass publishes them (batch statistics only).
+ *   neraf_debug_maxpool_fwd: stem BatchNorm + ReLU + MaxPool3d(3, 2, 1) of x [din^3][64] -> out [dout^3][64], dout = (din - 1) / 2 + 1,
+ *                            and, unless arg is NULL, the uint8 routing table [dout^3][64] (see neraf_resnet3d_debug_locate, kind 4).
+ *   neraf_debug_maxpool_bwd: the backward's routing: dpost [din^3 rounded up to 128][64] from the table and g [dout^3][64]. */
+int neraf_debug_bn_apply(neraf_ctx* ctx, const void* x, const float* const* bn5, int rep, const void* xr, const float* const* bn5_r,
+                         int rep_r, const void* res, int M, int Mpad, int C, int relu, float* fin_w, float* fin_w_r, void* out,
+                         int form, neraf_stream_t stream);
+int neraf_debug_maxpool_fwd(neraf_ctx* ctx, const void* x, const float* const* bn5, int rep, int din, void* out, void* arg,
+                            neraf_stream_t stream);
+int neraf_debug_maxpool_bwd(neraf_ctx* ctx, const void* arg, const void* g, int din, void* dpost, neraf_stream_t stream);
 
 /* Test hook (host only, no GPU needed): n / d as the gather kernels compute it -- the division-by-invariant constants of csrc/field_common.h
  * (make_fastdiv) with the multiply-high evaluated on the host.  d == 0 returns 0xFFFFFFFF. */

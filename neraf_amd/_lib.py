@@ -194,6 +194,10 @@ SIGNATURES = {
     "neraf_debug_fastdiv": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "neraf_resnet3d_debug_locate": (C.c_int, [C.POINTER(ResnetDesc), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                               C.POINTER(C.c_int)]),
+    "neraf_debug_bn_apply": (C.c_int, [C.c_void_p, C.c_void_p, c_fpp, C.c_int, C.c_void_p, c_fpp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "neraf_debug_maxpool_fwd": (C.c_int, [C.c_void_p, C.c_void_p, c_fpp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "neraf_debug_maxpool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "neraf_debug_conv_bn_relu_stage": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 11),
     "neraf_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

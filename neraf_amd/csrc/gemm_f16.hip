@@ -933,10 +933,11 @@ int launch_wide(neraf_ctx* ctx, const GemmParams& p, int splits, hipStream_t str
 // Streaming body for plain fp16 GEMMs with a short K and a narrow N (the 1x1x1 convolutions of ResNet3D layer 1 and their dgrads:
 // M = 32768, N x K = 256 x 64, 64 x 256, 64 x 64): 1 GFLOP against 20-40 MB, so the launch is a memory stream and the tile bodies
 // above -- one tile per CU, operand round trip, MFMAs, result image, atomics, nothing overlapping -- spend it in prologue and epilogue.
-// Here B (N * K <= 16384 elements, 32 KiB) is loaded ONCE per workgroup into LDS, rows K halfs apart with the 16-byte chunk index
-// XORed by the row (conflict-free ds_read_b128 fragments), and stays; a workgroup holds at most 128 of its columns, so N = 256 runs
-// as CS = 2 column slices, workgroup (row group rg, slice c), the two slices of a row group on the same XCD (one L2 serves A's second
-// reading).  A is walked in 64-row blocks by static assignment: the eight waves are two walkers of four waves, walker v = 2 rg + g
+// Here a workgroup's slice of B (NW = N / CS columns, NW * K <= 16384 elements, 32 KiB) is loaded ONCE into LDS, rows K halfs apart with
+// the 16-byte chunk index XORed by the row (conflict-free ds_read_b128 fragments), and stays; a workgroup holds at most 128 columns,
+// so N = 256 runs as CS = 2 column slices, workgroup (row group rg, slice c), the two slices of a row group on the same XCD (one L2
+// serves A's second reading).  CS is a template parameter: N x K = 128 x 256 (two slices of 64 columns) and 256 x 128 (two of 128)
+// run the same way -- the first 1x1x1 convolution of layer 2 on layer 1's 32768 voxels and its dgrad.  A is walked in 64-row blocks by static assignment: the eight waves are two walkers of four waves, walker v = 2 rg + g
 // takes blocks v, v + nv, v + 2 nv, ... (nv walkers in the launch; no dequeue, no synchronisation between workgroups, none between
 // waves inside the walk); wave w of a walker owns rows [16 w, 16 w + 16) of the block across the workgroup's columns:
 //   * its A operand never passes LDS: lane (row = lane & 15, q = lane >> 4) loads the 16 bytes A[row][32 kb + 8 q ..] per 32-deep K
@@ -964,14 +965,14 @@ __device__ __forceinline__ float row16_sum(float x) {
   return x;
 }
 
-template <int N, int K, bool STATS>
+template <int N, int K, int CS, bool STATS>
 __global__ __launch_bounds__(512) void gemm_f16_nt_stream_kernel(GemmParams p, int nblocks, int nrg) {
   constexpr int R = kStreamRows, KB = K / 32;
-  constexpr int CS = stream_slices(N), NW = N / CS, FNW = NW / 16;   // column slices of the launch; columns / fragments of a workgroup
+  constexpr int NW = N / CS, FNW = NW / 16;                     // CS column slices of the launch; columns / fragments of a workgroup
   constexpr int CPRB = K / 8, SWZ = (CPRB - 1) & 15;            // 16-byte chunks per B row; row bits XORed into the chunk index
   constexpr int BCH = NW * CPRB / 512;                          // B chunks a thread stages
   constexpr int IC = 64, NPASS = NW / IC, FNP = IC / 16, IMG_LD = IC + 8, CPR = IC / 8, IMG_WAVE = 16 * IMG_LD * 2;
-  static_assert(N * K <= 16384 && N % 64 == 0 && K % 64 == 0 && NW <= 128 && BCH >= 1, "B must fit 32 KiB of LDS");
+  static_assert(NW * K <= 16384 && NW % 64 == 0 && K % 64 == 0 && NW <= 128 && BCH >= 1, "a workgroup's slice of B must fit 32 KiB of LDS");
   static_assert(8 * 2 * NW * 4 <= 8 * IMG_WAVE, "the statistics' reduction re-uses the result images");
   __shared__ __attribute__((aligned(16))) char bs[NW * K * 2];
   __shared__ __attribute__((aligned(16))) char img_all[8 * IMG_WAVE];
@@ -1114,17 +1115,17 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_stream_kernel(GemmParams p, i
 
 // the shapes and epilogues the streaming body serves (everything ResNet3D layer 1 asks of a plain GEMM)
 static bool stream_qualifies(const GemmParams& p) {
-  const bool nk = (p.N == 64 || p.N == 128 || p.N == 256) && (p.K == 64 || p.K == 128 || p.K == 256) && p.N * p.K <= 16384;
+  // N * K <= 16384 with the slices of stream_slices(N); N x K = 128 x 256 and 256 x 128 as two slices of 32 KiB each
+  const bool nk = (p.N == 64 || p.N == 128 || p.N == 256) && (p.K == 64 || p.K == 128 || p.K == 256) && p.N * p.K <= 32768;
   return nk && p.Npad == p.N && p.conv.loader == 0 && p.ngroups <= 1 && !p.bf16 && (p.Mpad % kStreamRows) == 0 && p.C16 &&
          !p.bias && !p.act && !p.lmask && !p.C16T && !p.C32 && !p.alpha_dev && !p.bnb_x && !p.bnb_mask &&
          (!p.add16 || (p.ldadd % 4) == 0);
 }
 
-template <int N, int K>
+template <int N, int K, int CS = stream_slices(N)>
 int launch_stream_nk(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
   const int nblocks = p.Mpad / kStreamRows;
   // one workgroup of eight waves (two walkers) per CU and column slice of it: row groups = CUs / slices, never more than block pairs
-  constexpr int CS = stream_slices(N);
   int nrg = (ctx ? ctx->num_cus : 256) / CS;
   if (p.stream_max_wg > 0 && nrg > p.stream_max_wg / CS) nrg = p.stream_max_wg / CS;
   if (nrg > (nblocks + 1) / 2) nrg = (nblocks + 1) / 2;
@@ -1133,8 +1134,8 @@ int launch_stream_nk(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
   const double flops = p.alg_flops > 0.0 ? p.alg_flops : 2.0 * p.M * p.N * p.K;
   // accounted to the family the shape ran in before: 64-wide outputs to the 128x64 tile, the others to the wide body
   ProfScope prof(ctx, stream, N == 64 ? PROF_GEMM12864 : PROF_GEMM_WIDE, flops, 2.0 * p.M * p.N * p.K);
-  if (p.colsum || p.colsumsq) hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, true>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
-  else hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, false>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
+  if (p.colsum || p.colsumsq) hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, CS, true>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
+  else hipLaunchKernelGGL((gemm_f16_nt_stream_kernel<N, K, CS, false>), dim3(grid), dim3(512), 0, stream, p, nblocks, nrg);
   NERAF_HIP_CHECK(ctx, hipGetLastError());
   if (ctx && ctx->manifest) gemm_manifest(ctx, p, 0, 1, N, K, flops, false, true);
   return NERAF_OK;
@@ -1148,6 +1149,8 @@ int launch_stream(neraf_ctx* ctx, const GemmParams& p, hipStream_t stream) {
     case 128064: return launch_stream_nk<128, 64>(ctx, p, stream);
     case 128128: return launch_stream_nk<128, 128>(ctx, p, stream);
     case 256064: return launch_stream_nk<256, 64>(ctx, p, stream);
+    case 128256: return launch_stream_nk<128, 256, 2>(ctx, p, stream);       // two slices of 64 columns
+    case 256128: return launch_stream_nk<256, 128, 2>(ctx, p, stream);       // two slices of 128 columns
   }
   return neraf_fail(ctx, NERAF_EINVAL, "gemm: shape outside the streaming body's");
 }

@@ -64,35 +64,64 @@ __global__ __launch_bounds__(256) void bn_update_running_all_kernel(RunTable t, 
 // stem: out[32^3-like][64] = maxpool3(s2,p1)( relu(bn(x)) ), x pre-BN [din^3][64]
 // arg (training): tap index (dz+1)*9 + (dy+1)*3 + (dx+1) of the FIRST maximum of each window, 255 when the maximum is not > 0 --
 // the routing table of the backward (maxpool_bwd_gather_kernel)
+//
+// One output voxel-chunk (8 channels) per thread.  The 27 taps are requested a z-plane at a time -- nine 16-byte loads from the
+// coordinates clamped into the image, no branch between them, the first two planes before the statistics -- where a walk that loaded
+// tap by tap behind three nested bounds checks waited for 27 dependent round trips to the L1 / L2.  A tap outside the image is loaded
+// (from its clamped neighbour) but never compared: the taps are visited in the (dz, dy, dx) order with the same skip, the same
+// fmaf / fmaxf in fp32 and the same strict '>' as before, so value and routing table are unchanged bit for bit.
+inline unsigned pool_blocks(int dout) { return (unsigned)((cube(dout) * 8 + 255) / 256); }
+
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(BnSrc s, int din, int dout, size_t m_in, half_t* __restrict__ out,
                                                              unsigned char* __restrict__ arg) {
-  __shared__ float sc[64], sh[64];
-  if (threadIdx.x < 64) bn_scale_shift(s, threadIdx.x, 1.f / (float)m_in, sc[threadIdx.x], sh[threadIdx.x]);
-  __syncthreads();
+  __shared__ __attribute__((aligned(16))) float sc[64], sh[64];
   const size_t total = cube(dout) * 8;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const size_t vox = idx >> 3; const int c0 = (int)(idx & 7) * 8;
+  const bool active = idx < total;
+  const size_t vox = active ? idx >> 3 : 0; const int c0 = (int)(idx & 7) * 8;
   const int x = (int)(vox % dout), y = (int)((vox / dout) % dout), z = (int)(vox / ((size_t)dout * dout));
+  bool okz[3], oky[3], okx[3];
+  size_t offy[3], offx[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    okz[d] = (unsigned)(2 * z + d - 1) < (unsigned)din; oky[d] = (unsigned)(2 * y + d - 1) < (unsigned)din; okx[d] = (unsigned)(2 * x + d - 1) < (unsigned)din;
+    offy[d] = (size_t)min(max(2 * y + d - 1, 0), din - 1) * din * 64;
+    offx[d] = (size_t)min(max(2 * x + d - 1, 0), din - 1) * 64 + c0;
+  }
+  auto load_plane = [&](int d, uint4 (&pl)[9]) {
+    const half_t* base = s.x + (size_t)min(max(2 * z + d - 1, 0), din - 1) * din * din * 64;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) pl[t] = *reinterpret_cast<const uint4*>(base + offy[t / 3] + offx[t % 3]);
+  };
+  uint4 pa[9], pb[9];
+  load_plane(0, pa);
+  load_plane(1, pb);
+  if (threadIdx.x < 64) bn_scale_shift(s, threadIdx.x, 1.f / (float)m_in, sc[threadIdx.x], sh[threadIdx.x]);
+  __syncthreads();
+  if (!active) return;
+  float scv[8], shv[8];
+  *reinterpret_cast<f32x4*>(scv) = *reinterpret_cast<const f32x4*>(sc + c0); *reinterpret_cast<f32x4*>(scv + 4) = *reinterpret_cast<const f32x4*>(sc + c0 + 4);
+  *reinterpret_cast<f32x4*>(shv) = *reinterpret_cast<const f32x4*>(sh + c0); *reinterpret_cast<f32x4*>(shv + 4) = *reinterpret_cast<const f32x4*>(sh + c0 + 4);
   float best[8]; int at[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { best[j] = -3.0e38f; at[j] = 255; }
-  for (int dz = -1; dz <= 1; ++dz) {
-    const int iz = 2 * z + dz; if ((unsigned)iz >= (unsigned)din) continue;
-    for (int dy = -1; dy <= 1; ++dy) {
-      const int iy = 2 * y + dy; if ((unsigned)iy >= (unsigned)din) continue;
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int ix = 2 * x + dx; if ((unsigned)ix >= (unsigned)din) continue;
-        const half8 v = *reinterpret_cast<const half8*>(s.x + (((size_t)iz * din + iy) * din + ix) * 64 + c0);
-        const int tap = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1);
+  auto reduce_plane = [&](int d, const uint4 (&pl)[9]) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float a = fmaxf(fmaf((float)v[j], sc[c0 + j], sh[c0 + j]), 0.f);
-          if (a > best[j]) { best[j] = a; at[j] = tap; }
-        }
+    for (int t = 0; t < 9; ++t) {
+      if (!(okz[d] && oky[t / 3] && okx[t % 3])) continue;
+      const half8 v = *reinterpret_cast<const half8*>(&pl[t]);
+      const int tap = d * 9 + t;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float a = fmaxf(fmaf((float)v[j], scv[j], shv[j]), 0.f);
+        if (a > best[j]) { best[j] = a; at[j] = tap; }
       }
     }
-  }
+  };
+  reduce_plane(0, pa);
+  load_plane(2, pa);
+  reduce_plane(1, pb);
+  reduce_plane(2, pa);
   if (arg) {
     unsigned long long packed = 0ull;
 #pragma unroll
@@ -195,6 +224,43 @@ extern "C" int neraf_resnet3d_debug_locate(const neraf_resnet3d_desc* d, int kin
   return NERAF_EINVAL;
 }
 
+// Test entries: ONE element-wise pass of the forward on caller tensors (the kernels live in the anonymous namespace).
+// bn5 = HOST array {stats, gamma, beta, running_mean, running_var} of device pointers; stats = null selects the running statistics.
+static BnSrc debug_bn_src(const void* x, const float* const* bn5, int rep, int C, float* fin_w) {
+  BnSrc s{};
+  s.read_mode = bn_stat_read_mode();
+  s.x = (const half_t*)x;
+  s.stats = bn5[0]; s.fin_w = bn5[0] ? fin_w : nullptr;
+  s.gamma = bn5[1]; s.beta = bn5[2]; s.rmean = bn5[3]; s.rvar = bn5[4];
+  s.cpad = round_up(C, 128); s.rep = rep;
+  return s;
+}
+
+extern "C" int neraf_debug_bn_apply(neraf_ctx* ctx, const void* x, const float* const* bn5, int rep, const void* xr,
+                                    const float* const* bn5_r, int rep_r, const void* res, int M, int Mpad, int C, int relu,
+                                    float* fin_w, float* fin_w_r, void* out, int form, neraf_stream_t stream) {
+  if (!x || !bn5 || !out || (xr && (!bn5_r || res)) || M < 1 || Mpad < M || Mpad % 128 || C < 8 || C % 8 || form < 0 || form > 1 ||
+      rep < 1 || rep > 16 || (xr && (rep_r < 1 || rep_r > 16)) || ((rep > 1 || (xr && rep_r > 1)) && 2 * round_up(C, 128) > kStatStride))
+    return neraf_fail(ctx, NERAF_EINVAL, "debug_bn_apply: bad arguments");
+  BnApplyArgs a{};
+  a.a = debug_bn_src(x, bn5, rep, C, fin_w);
+  if (xr) a.r = debug_bn_src(xr, bn5_r, rep_r, C, fin_w_r);
+  a.res = (const half_t*)res;
+  a.M = M; a.Mpad = Mpad; a.C = C; a.relu = relu; a.out = (half_t*)out;
+  return run_bn_apply(ctx, (hipStream_t)stream, a, form);
+}
+
+extern "C" int neraf_debug_maxpool_fwd(neraf_ctx* ctx, const void* x, const float* const* bn5, int rep, int din, void* out, void* arg,
+                                       neraf_stream_t stream) {
+  if (!x || !bn5 || !out || din < 2 || din > 256 || rep < 1 || rep > 16) return neraf_fail(ctx, NERAF_EINVAL, "debug_maxpool_fwd: bad arguments");
+  const int dout = (din - 1) / 2 + 1;
+  BnSrc s = debug_bn_src(x, bn5, rep, 64, nullptr);
+  hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(pool_blocks(dout)), dim3(256), 0, (hipStream_t)stream, s, din, dout, cube(din),
+                     (half_t*)out, (unsigned char*)arg);
+  NERAF_HIP_CHECK(ctx, hipGetLastError());
+  return NERAF_OK;
+}
+
 extern "C" int neraf_resnet3d_pack_weights(neraf_ctx* ctx, const neraf_resnet3d_desc* d, const float* const* conv_w, void* packed,
                                            neraf_stream_t stream) {
   Arch A; Layout L;
@@ -261,8 +327,7 @@ static int resnet3d_fwd_body(neraf_ctx* ctx, const Arch& A, const Layout& L, con
   {
     const ConvSpec& c = A.conv[0];
     BnSrc s = bn_src_fwd(A, L, ws, bn, 0, use_batch_stats);
-    const size_t total = cube(A.pooled) * 8;
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, s, c.dout, A.pooled,
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(pool_blocks(A.pooled)), dim3(256), 0, st, s, c.dout, A.pooled,
                        cube(c.dout), (half_t*)(ws + L.act_pool), training ? (unsigned char*)(ws + L.pool_arg) : nullptr);
     NERAF_HIP_CHECK(ctx, hipGetLastError());
     neraf_node(ctx, "bn_relu_maxpool_kernel | stem BatchNorm + ReLU + 3x3x3/2 max-pool", 0.0, (double)cube(c.dout) * 64 * 2.0,

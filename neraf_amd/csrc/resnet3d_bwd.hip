@@ -417,40 +417,100 @@ __global__ __launch_bounds__(256) void bwd_prologue_kernel(const float* __restri
 // replaced re-evaluated the 27 taps of every window and added fp32 atomics into a zeroed 67 MB buffer: 74 + 10 us).
 // An input coordinate i belongs to window o = i/2 through tap d = 0 when i is even, and to windows (i-1)/2 (d = +1) and
 // (i+1)/2 (d = -1) when it is odd: at most 8 windows per voxel.
+//
+// Work is dealt by CELLS of 2 x 2 x 2 input voxels (2c .. 2c+1 per axis): a cell holds one voxel of each parity class -- 1, 2, 2, 2,
+// 4, 4, 4 and 8 windows -- so every thread (one cell, 8 channels) does the same 27 compares where a thread per voxel left seven
+// lanes in eight waiting for the all-odd one; and all windows its voxels belong to are the 8 windows c .. c+1 per axis, whose
+// (arg, g) pairs the thread reads ONCE.  A workgroup owns kGatherCz x kGatherCy x kGatherCx cells and first stages the
+// (cz+1)(cy+1)(cx+1) windows they touch in LDS (windows past the last one: arg 255, which equals no tap).  Per voxel the
+// contributions are added in the order of the per-voxel gather -- window (i-1)/2 before (i+1)/2 per axis, z outermost, x innermost,
+// fp32 from 0, one rounding to fp16 -- so the result is that gather's bit for bit.  Workgroup 0 also writes the zero rows
+// [din^3, rows_pad_in).
+constexpr int kGatherCz = 2, kGatherCy = 4, kGatherCx = 4;
+constexpr int kGatherWin = (kGatherCz + 1) * (kGatherCy + 1) * (kGatherCx + 1);      // 75 windows: 4800 + 9600 bytes
+static_assert(kGatherCz * kGatherCy * kGatherCx * 8 == 256, "one cell-chunk per thread");
+
+inline unsigned gather_blocks(int din) {
+  const int nc = (din + 1) / 2;
+  return (unsigned)(((nc + kGatherCz - 1) / kGatherCz) * ((nc + kGatherCy - 1) / kGatherCy) * ((nc + kGatherCx - 1) / kGatherCx));
+}
+
 __global__ __launch_bounds__(256) void maxpool_bwd_gather_kernel(const unsigned char* __restrict__ arg, int din, int dout,
                                                                 const half_t* __restrict__ g, half_t* __restrict__ dpost, size_t rows_pad_in) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows_pad_in * 8) return;
-  const size_t vox = idx >> 3; const int c0 = (int)(idx & 7) * 8;
-  float acc[8];
+  __shared__ unsigned long long s_arg[kGatherWin * 8];
+  __shared__ uint4 s_g[kGatherWin * 8];
+  const int tid = threadIdx.x;
+  const int nc = (din + 1) / 2;
+  const int nbx = (nc + kGatherCx - 1) / kGatherCx, nby = (nc + kGatherCy - 1) / kGatherCy;
+  const int bx = blockIdx.x % nbx, by = (blockIdx.x / nbx) % nby, bz = blockIdx.x / (nbx * nby);
+  const int oz0 = bz * kGatherCz, oy0 = by * kGatherCy, ox0 = bx * kGatherCx;
+  {
+    // all requests of the thread before the first LDS write; windows past the end are read at the clamped coordinate (no branch
+    // between the requests) and replaced
+    constexpr int kSt = (kGatherWin * 8 + 255) / 256;
+    unsigned long long am_s[kSt]; uint4 g_s[kSt]; bool inside[kSt];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (vox < cube(din)) {
-    const int ix = (int)(vox % din), iy = (int)((vox / din) % din), iz = (int)(vox / ((size_t)din * din));
-    int oz[2], tz[2], oy[2], ty[2], ox[2], tx[2];
-    auto wins = [&](int i, int (&o)[2], int (&tp)[2]) {
-      if ((i & 1) == 0) { o[0] = i >> 1; tp[0] = 1; return 1; }
-      o[0] = (i - 1) >> 1; tp[0] = 2;                    // d = +1
-      if (((i + 1) >> 1) < dout) { o[1] = (i + 1) >> 1; tp[1] = 0; return 2; }
-      return 1;
-    };
-    const int nz = wins(iz, oz, tz), ny = wins(iy, oy, ty), nx = wins(ix, ox, tx);
-    for (int a = 0; a < nz; ++a)
-      for (int b = 0; b < ny; ++b)
-        for (int c = 0; c < nx; ++c) {
-          const size_t ov = ((size_t)oz[a] * dout + oy[b]) * dout + ox[c];
-          const unsigned tap = (unsigned)(tz[a] * 9 + ty[b] * 3 + tx[c]);
-          const unsigned long long am = *reinterpret_cast<const unsigned long long*>(arg + ov * 64 + c0);
-          const half8 gv = *reinterpret_cast<const half8*>(g + ov * 64 + c0);
+    for (int k = 0; k < kSt; ++k) {
+      const int e = min(k * 256 + tid, kGatherWin * 8 - 1);
+      const int w = e >> 3;
+      const int oz = oz0 + w / ((kGatherCx + 1) * (kGatherCy + 1)), oy = oy0 + (w / (kGatherCx + 1)) % (kGatherCy + 1), ox = ox0 + w % (kGatherCx + 1);
+      inside[k] = oz < dout && oy < dout && ox < dout;
+      const size_t ov = ((size_t)min(oz, dout - 1) * dout + min(oy, dout - 1)) * dout + min(ox, dout - 1);
+      am_s[k] = *reinterpret_cast<const unsigned long long*>(arg + ov * 64 + (e & 7) * 8);
+      g_s[k] = *reinterpret_cast<const uint4*>(g + ov * 64 + (e & 7) * 8);
+    }
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (((am >> (8 * j)) & 0xffu) == tap) acc[j] += (float)gv[j];
-        }
+    for (int k = 0; k < kSt; ++k) {
+      const int e = k * 256 + tid;
+      if (e < kGatherWin * 8) { s_arg[e] = inside[k] ? am_s[k] : ~0ull; s_g[e] = inside[k] ? g_s[k] : make_uint4(0u, 0u, 0u, 0u); }
+    }
   }
-  half8 o;
+  if (blockIdx.x == 0) {
+    const size_t first = cube(din) * 8, total = rows_pad_in * 8;
+    for (size_t e = first + tid; e < total; e += 256) reinterpret_cast<uint4*>(dpost)[e] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  const int ch = tid & 7, lc = tid >> 3;
+  const int lx = lc % kGatherCx, ly = (lc / kGatherCx) % kGatherCy, lz = lc / (kGatherCx * kGatherCy);
+  unsigned long long am[8];
+  half8 gv[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (half_t)acc[j];      // at most 8 windows meet in a voxel: inside the group's headroom, and measured by the consumer
-  *reinterpret_cast<half8*>(dpost + vox * 64 + c0) = o;
+  for (int k = 0; k < 8; ++k) {
+    const int w = ((lz + (k >> 2)) * (kGatherCy + 1) + ly + ((k >> 1) & 1)) * (kGatherCx + 1) + lx + (k & 1);
+    am[k] = s_arg[w * 8 + ch];
+    const uint4 raw = s_g[w * 8 + ch];
+    gv[k] = *reinterpret_cast<const half8*>(&raw);
+  }
+  // a voxel of parity p on an axis: p = 0 -> window offset 0 through tap 1; p = 1 -> offset 0 through tap 2 (d = +1), then offset 1
+  // through tap 0 (d = -1)
+#pragma unroll
+  for (int pz = 0; pz < 2; ++pz)
+#pragma unroll
+    for (int py = 0; py < 2; ++py)
+#pragma unroll
+      for (int px = 0; px < 2; ++px) {
+        const int iz = 2 * (oz0 + lz) + pz, iy = 2 * (oy0 + ly) + py, ix = 2 * (ox0 + lx) + px;
+        if (iz >= din || iy >= din || ix >= din) continue;
+        float acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int a = 0; a <= pz; ++a)
+#pragma unroll
+          for (int b = 0; b <= py; ++b)
+#pragma unroll
+            for (int c = 0; c <= px; ++c) {
+              const unsigned tap = (unsigned)((pz ? 2 - 2 * a : 1) * 9 + (py ? 2 - 2 * b : 1) * 3 + (px ? 2 - 2 * c : 1));
+              const int k = a * 4 + b * 2 + c;
+#pragma unroll
+              for (int j = 0; j < 8; ++j)
+                if (((am[k] >> (8 * j)) & 0xffu) == tap) acc[j] += (float)gv[k][j];
+            }
+        half8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (half_t)acc[j];      // at most 8 windows meet in a voxel: inside the group's headroom, and measured by the consumer
+        *reinterpret_cast<half8*>(dpost + (((size_t)iz * din + iy) * din + ix) * 64 + ch * 8) = o;
+      }
 }
 
 __global__ void set_f32x2_kernel(float* p, float a, float b) { if (threadIdx.x == 0 && blockIdx.x == 0) { p[0] = a; p[1] = b; } }
@@ -841,7 +901,7 @@ static int resnet3d_bwd_body(neraf_ctx* ctx, const Arch& A, const Layout& L, con
     const ConvSpec& c0 = A.conv[0];
     half_t* dpost = (half_t*)(bws + B.dpost);          // the fp32-sized buffer, used as fp16
     const size_t rp = rows_pad(c0.dout);
-    hipLaunchKernelGGL(maxpool_bwd_gather_kernel, dim3((unsigned)((rp * 8 + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(maxpool_bwd_gather_kernel, dim3(gather_blocks(c0.dout)), dim3(256), 0, st,
                        (const unsigned char*)(ws + L.pool_arg), c0.dout, A.pooled, g, dpost, rp);
     NERAF_HIP_CHECK(ctx, hipGetLastError());
     neraf_node(ctx, "maxpool_bwd_gather_kernel | max-pool routing", 0.0, (double)cube(A.pooled) * 64 * 3.0, (double)rp * 64 * 2.0);
@@ -992,6 +1052,16 @@ extern "C" int neraf_resnet3d_bwd_chain_state(neraf_ctx* ctx, const neraf_resnet
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Test entry: the max-pool routing of the backward alone.  arg uint8 [dout^3][64] (the forward's table), g fp16 [dout^3][64],
+// dout = (din - 1) / 2 + 1; writes dpost fp16 [round_up(din^3, 128)][64].
+extern "C" int neraf_debug_maxpool_bwd(neraf_ctx* ctx, const void* arg, const void* g, int din, void* dpost, neraf_stream_t stream) {
+  if (!arg || !g || !dpost || din < 2 || din > 256) return neraf_fail(ctx, NERAF_EINVAL, "debug_maxpool_bwd: bad arguments");
+  hipLaunchKernelGGL(maxpool_bwd_gather_kernel, dim3(gather_blocks(din)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)arg,
+                     din, (din - 1) / 2 + 1, (const half_t*)g, (half_t*)dpost, rows_pad(din));
+  NERAF_HIP_CHECK(ctx, hipGetLastError());
+  return NERAF_OK;
+}
+
 // Test entry: ONE conv + BatchNorm(train) + ReLU stage, forward statistics and backward, on caller data.  The full
 // encoder is chaotic under fp16 rounding through its ReLU gates, so besides the gate-matched full-chain test
 // (tests/test_gpu_resnet3d.py::test_resnet3d_backward_gate_matched) the backward kernels are verified stage by stage against

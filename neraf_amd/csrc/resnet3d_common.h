@@ -480,14 +480,87 @@ inline int run_conv(neraf_ctx* ctx, hipStream_t st, const Arch& A, const Layout&
   return NERAF_OK;
 }
 
-inline int run_bn_apply(neraf_ctx* ctx, hipStream_t st, const BnApplyArgs& a) {
+// The same pass for tensors of kBnTileMinChunks chunks or more (all of layer 1, the wide ones of layers 2-3), grid (Mpad / (32 U), C / 64): a workgroup owns a tile of 32 U rows x 64
+// channels, every thread U chunks per operand, ALL requested before the first use -- the whole tensor is in flight in one wave of
+// workgroups, where bn_apply_kernel's 2048 workgroups take their chunks one after the other (load -> store -> next load: two to
+// four dependent HBM round trips at 32768 x 256).  A workgroup also builds the table of ITS 64 channels only: the replicated
+// accumulators are read past the L2 (stat_ld), and 2048 workgroups reading all C channels of 16 replicas are 64 MB of such
+// reads at C = 256 against 50 MB of tensor -- here 16 MB.  The geometry is bn_bwd_apply_kernel's, the yardstick on these tensors.
+// Per element the arithmetic is bn_apply_kernel's to the letter (same table through bn_scale_shift, same fmaf, same order of
+// residual / bn_r add, relu and conversion), so the two forms agree bit for bit (tests/test_gpu_bn_apply_forms.py).
+template <int U>
+__global__ __launch_bounds__(256) void bn_apply_tile_kernel(BnApplyArgs p) {
+  __shared__ __attribute__((aligned(16))) float sc[64], sh[64], scr[64], shr[64];
+  const int tid = threadIdx.x;
+  const int c_base = blockIdx.y * 64, c0 = (tid & 7) * 8;
+  const int m0 = blockIdx.x * (32 * U) + (tid >> 3);
+  const float inv_m = 1.f / (float)p.M;
+  const half_t* second = p.r.x ? p.r.x : p.res;
+  half8 x[U], rr[U];
+#pragma unroll
+  for (int it = 0; it < U; ++it) {
+    const int row = m0 + it * 32;
+    if (row < p.M) {
+      const size_t off = (size_t)row * p.C + c_base + c0;
+      x[it] = *reinterpret_cast<const half8*>(p.a.x + off);
+      if (second) rr[it] = *reinterpret_cast<const half8*>(second + off);
+    }
+  }
+  if (tid < 64) bn_scale_shift(p.a, c_base + tid, inv_m, sc[tid], sh[tid]);
+  else if (tid < 128 && p.r.x) bn_scale_shift(p.r, c_base + tid - 64, inv_m, scr[tid - 64], shr[tid - 64]);
+  __syncthreads();
+  float scv[8], shv[8], scrv[8], shrv[8];
+  *reinterpret_cast<f32x4*>(scv) = *reinterpret_cast<const f32x4*>(sc + c0); *reinterpret_cast<f32x4*>(scv + 4) = *reinterpret_cast<const f32x4*>(sc + c0 + 4);
+  *reinterpret_cast<f32x4*>(shv) = *reinterpret_cast<const f32x4*>(sh + c0); *reinterpret_cast<f32x4*>(shv + 4) = *reinterpret_cast<const f32x4*>(sh + c0 + 4);
+  if (p.r.x) {
+    *reinterpret_cast<f32x4*>(scrv) = *reinterpret_cast<const f32x4*>(scr + c0); *reinterpret_cast<f32x4*>(scrv + 4) = *reinterpret_cast<const f32x4*>(scr + c0 + 4);
+    *reinterpret_cast<f32x4*>(shrv) = *reinterpret_cast<const f32x4*>(shr + c0); *reinterpret_cast<f32x4*>(shrv + 4) = *reinterpret_cast<const f32x4*>(shr + c0 + 4);
+  }
+#pragma unroll
+  for (int it = 0; it < U; ++it) {
+    const int row = m0 + it * 32;             // < Mpad: the grid covers Mpad / (32 U) row tiles exactly
+    half8 o;
+    if (row < p.M) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = fmaf((float)x[it][j], scv[j], shv[j]);
+        if (p.r.x) v += fmaf((float)rr[it][j], scrv[j], shrv[j]);
+        else if (p.res) v += (float)rr[it][j];
+        if (p.relu) v = fmaxf(v, 0.f);
+        o[j] = (half_t)v;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = (half_t)0.f;
+    }
+    *reinterpret_cast<half8*>(p.out + (size_t)row * p.C + c_base + c0) = o;
+  }
+}
+
+// Which form runs: the tile form from kBnTileMinChunks 16-byte chunks per operand on.  Measured over the encoder's shapes
+// (tools/bn_apply_bench.py, profiles/stream_passes_ab.txt): it wins from 512 x 1024 and 4096 x 128 (65536 chunks) upwards -- most
+// where C is large, a table of 64 channels instead of C -- and draws at 512 x 256, which keeps bn_apply_kernel and its single
+// hoisted load.  U = 2 (64 rows per workgroup): U = 4 gains 0.6 us at 32768 x 256 and loses at every smaller shape.
+constexpr size_t kBnTileMinChunks = (size_t)1 << 16;
+constexpr int kBnTileU = 2;
+inline bool bn_tile_fits(const BnApplyArgs& a) { return a.C % 64 == 0 && a.Mpad % (32 * kBnTileU) == 0; }
+
+// form: -1 the selector above, 0 bn_apply_kernel, 1 bn_apply_tile_kernel (the test entry neraf_debug_bn_apply forces either)
+inline int run_bn_apply(neraf_ctx* ctx, hipStream_t st, const BnApplyArgs& a, int form = -1) {
   const size_t total = (size_t)a.Mpad * (a.C >> 3);
-  long blocks = (long)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)blocks), dim3(256), (size_t)4 * a.C * sizeof(float), st, a);
+  if (form == 1 && !bn_tile_fits(a)) return neraf_fail(ctx, NERAF_EINVAL, "bn_apply: the tile form needs C % 64 == 0 and Mpad % 64 == 0");
+  const bool tile = form < 0 ? (total >= kBnTileMinChunks && bn_tile_fits(a)) : form == 1;
+  if (tile) {
+    hipLaunchKernelGGL(bn_apply_tile_kernel<kBnTileU>,dim3((unsigned)(a.Mpad / (32 * kBnTileU)), (unsigned)(a.C / 64)), dim3(256), 0, st, a);
+  } else {
+    long blocks = (long)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)blocks), dim3(256), (size_t)4 * a.C * sizeof(float), st, a);
+  }
   if (ctx && ctx->manifest) {
     char nm[96];
-    snprintf(nm, sizeof(nm), "bn_apply_kernel | M=%d C=%d%s", a.M, a.C, a.r.x ? " + bn(downsample)" : (a.res ? " + residual" : ""));
+    snprintf(nm, sizeof(nm), "%s | M=%d C=%d%s", tile ? "bn_apply_tile_kernel" : "bn_apply_kernel", a.M, a.C,
+             a.r.x ? " + bn(downsample)" : (a.res ? " + residual" : ""));
     neraf_node(ctx, nm, 0.0, (double)a.M * a.C * 2.0 * ((a.r.x || a.res) ? 2 : 1), (double)a.Mpad * a.C * 2.0);
   }
   NERAF_HIP_CHECK(ctx, hipGetLastError());

@@ -14,9 +14,12 @@ from neraf_amd import _lib
 lib = _lib.load(); h = _lib.ctx(0)
 dev = torch.device("cuda:0")
 # (N, K, add16, statistics): the rows of the layer-1 table -- forward 64 -> 256, its dgrad with the residual gradient added,
-# forward 256 -> 64 and its dgrads, the 64 -> 64 pair; then the two (N, K) the body serves that layer 1 does not use
+# forward 256 -> 64 and its dgrads, the 64 -> 64 pair; then the three (N, K) the body serves that layer 1 does not use
 SHAPES = [(256, 64, 0, 1), (256, 64, 1, 0), (64, 256, 0, 1), (64, 256, 1, 0), (64, 64, 0, 1), (64, 64, 0, 0), (128, 128, 0, 1), (128, 64, 0, 1),
-          (64, 128, 0, 1)]
+          (64, 128, 0, 1),
+          # the two shapes that run as two column slices of 32 KiB of B each: layer 2's first 1x1x1 convolution (256 -> 128 on the
+          # 32768 voxels of layer 1's output) and its dgrad
+          (128, 256, 0, 1), (256, 128, 0, 0)]
 NB = int(os.environ.get("NB_BUFFERS", "8"))
 NL, R = 24, 20
 Ms = [int(a) for a in sys.argv[1:]] or [32768]

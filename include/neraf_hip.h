@@ -476,7 +476,8 @@ int neraf_resnet3d_update_running_stats(neraf_ctx* ctx, const neraf_resnet3d_des
                                         neraf_stream_t stream);
 
 /* Backward of neraf_resnet3d_fwd (train-mode BatchNorm).  `workspace` is the forward's (its activations and
- * BN statistics are read); packed_t comes from neraf_resnet3d_pack_weights_bwd.  dfeat fp32 [1024] ->
+ * BN statistics are read); packed_t comes from neraf_resnet3d_pack_weights_bwd of the CURRENT weights (the dgrad matrices and the
+ * stem filter's fp32 table for the grid gradient, which is read from there and not from conv_w).  dfeat fp32 [1024] ->
  * w_grads (HOST array, 43 device pointers shaped like the Conv3d weights, overwritten) and bn_grads (HOST
  * array, 2 per BatchNorm3d: d weight, d bias).  If n_cells > 0 the gradient w.r.t. channels [0, n_ch) of
  * the grid cells [cell_start, cell_start+n_cells) (flat x-major index, the refresh window of
@@ -510,6 +511,22 @@ int neraf_manifest_get(neraf_ctx* ctx, int index, char* name, int name_cap, doub
 int neraf_debug_conv_bn_relu_stage(neraf_ctx* ctx, int cin, int cin_real, int cout, int k, int stride, int pad, int din,
                                    const void* x_f16, const float* w, const float* gamma, const float* beta, const float* g,
                                    void* y_f16, float* dx, float* dw, float* dgamma, float* dbeta, neraf_stream_t stream);
+
+/* Test aids: the strided convolution launches alone, on caller buffers (allocate and synchronise internally; not part of the product path).
+ *   neraf_debug_stem_conv:      the raw stem convolution (8 stored channels of which cin_real carry weights -> 64, 5^3, stride 2, pad 2):
+ *                               x fp16 [din^3][8], w fp32 [64][cin_real][125] -> y fp16 [(din/2)^3 rounded up to 128 rows][64] (pre-BatchNorm;
+ *                               rows past the result are zeros) and sums fp32 [2][128]: column sums and sums of squares of y (cleared first).
+ *   neraf_debug_conv_transpose: the dgrad GEMM of a k^3 (k = 1 or 3), stride-2, pad k/2 convolution cin -> cout with input edge din:
+ *                               dy fp16 [(din/2)^3][cout], w fp32 [cout][cin][k^3] -> dx fp16 [din^3][cin]; in_place != 0 adds into dx
+ *                               (add16 == destination), else dx is overwritten.  din even, din^3 a multiple of 128, cin and cout of 64.
+ *   neraf_debug_stem_dgrid:     the stem's input (grid) gradient for the window of n_cells cells from cell `start` of the S^3 grid (cell =
+ *                               (z S + y) S + x): dy fp16 [(S/2)^3][64], w fp32 [64][7][125] -> out fp32 [n_ch][n_cells], scaled by inv_scale. */
+int neraf_debug_stem_conv(neraf_ctx* ctx, int din, int cin_real, const void* x_f16, const float* w, void* y_f16, float* sums,
+                          neraf_stream_t stream);
+int neraf_debug_conv_transpose(neraf_ctx* ctx, int cin, int cout, int k, int din, const void* dy_f16, const float* w, void* dx_f16,
+                               int in_place, neraf_stream_t stream);
+int neraf_debug_stem_dgrid(neraf_ctx* ctx, int S, const void* dy_f16, const float* w, unsigned long long start, int n_cells, int n_ch,
+                           float inv_scale, float* out, neraf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Camera-pose refinement on a ray bundle (nerfstudio CameraOptimizer(mode="SO3xR3").apply_to_raybundle, NeRAF_config.py:97):

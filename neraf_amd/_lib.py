@@ -199,6 +199,10 @@ SIGNATURES = {
     "neraf_debug_maxpool_fwd": (C.c_int, [C.c_void_p, C.c_void_p, c_fpp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "neraf_debug_maxpool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "neraf_debug_conv_bn_relu_stage": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 11),
+    "neraf_debug_stem_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "neraf_debug_stem_dgrid": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                         C.c_void_p]),
+    "neraf_debug_conv_transpose": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     "neraf_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }

@@ -194,7 +194,9 @@ struct ConvGeom {
   int tstride;   // transposed convolution of a stride-2 conv: a tap contributes only where (z + pad - tap) is even
   int tclass;    // (set by the dispatcher) tstride == 2 with PARITY-CLASS row order: M-tile t holds 64 result voxels of parity class
                  // t & 7 = (z&1, y&1, x&1), so the tile walks only the taps that reach that class (27 -> 1, 2, 4 or 8 of a 3x3x3 filter;
-                 // 27/8 on average instead of 27 with 7/8 of the rows fed from the zero page); the epilogue maps rows back to voxels
+                 // 27/8 on average instead of 27 with 7/8 of the rows fed from the zero page); the epilogue maps rows back to voxels.
+                 // 1: classes alternate tile by tile; 2: every XCD walks its tiles heaviest class first (3x3x3); 3: the strided 1x1x1
+                 // dgrad added in place, launched as a plain GEMM over the one reaching class (rows = source voxels)
   const half_t* zero_page;   // >= 16 bytes of zeros: source of every out-of-bounds / padding-tap chunk
 };
 

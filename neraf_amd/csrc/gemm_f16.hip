@@ -73,17 +73,24 @@ __device__ __forceinline__ void tclass_coords(const ConvGeom& g, int m, int& z, 
   const int x2 = r % h, y2 = (r / h) % h, z2 = r / (h * h);
   z = 2 * z2 + ((cls >> 2) & 1); y = 2 * y2 + ((cls >> 1) & 1); x = 2 * x2 + (cls & 1);
 }
-template <int BM, bool TC>
+// Row maps of the epilogue (RMAP): 0 row m is result row m; 1 parity-class rows (above); 2 the COMPACT strided 1x1x1 dgrad -- GEMM row m
+// is source voxel m of the (dout / 2)^3 gradient and lands on result voxel (2z, 2y, 2x), the only class its one tap reaches.
+template <int BM, int RMAP>
 __device__ __forceinline__ int out_row(const GemmParams& p, int m) {
-  if (!TC) return m;
+  if (RMAP == 0) return m;
   int z, y, x;
-  tclass_coords<BM>(p.conv, m, z, y, x);
+  if (RMAP == 2) {
+    const int h = p.conv.dout >> 1;
+    x = 2 * (m % h); y = 2 * ((m / h) % h); z = 2 * (m / (h * h));
+  } else {
+    tclass_coords<BM>(p.conv, m, z, y, x);
+  }
   return (z * p.conv.dout + y) * p.conv.dout + x;
 }
 
 // ------------------------------------------------------------------------------------------------------
 // Epilogue of the GEMM kernel (the split-K reducer applies the same operations element-wise).
-template <int BM, int BN, bool BF, int WAVES_M = 2, bool TC = false>
+template <int BM, int BN, bool BF, int WAVES_M = 2, int TC = 0>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[Tile<BM, BN, WAVES_M>::FM][Tile<BM, BN, WAVES_M>::FN],
                                               char* smem, int bm, int bn, int lane, int wave, int M, int N, float* C32, int ldc32) {
   using T = Tile<BM, BN, WAVES_M>;
@@ -352,15 +359,29 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
   const int first_m = group * GROUP_M;
   const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
   const int in_group = bid - group * GROUP_M * tiles_n;
-  const int bm = first_m + in_group % gsz;
-  const int bn = in_group / gsz;
+  int bm = first_m + in_group % gsz;
+  int bn = in_group / gsz;
 
   // parity-class rows of a stride-2 transposed convolution: this tile's class walks taps t0 + 2i per axis only
   constexpr bool tclass = LOADER == 1 && TC;     // compile-time: the tap decode below must not weigh on the ordinary conv loaders
+  constexpr int RMAP = TC ? (LOADER == 1 ? 1 : 2) : 0;      // the epilogue's row map (out_row)
   int t0z = 0, t0y = 0, t0x = 0, cy = KS, cx = KS;
   int nk_total = p.K / BK;
   if (tclass) {
-    const int cls = bm & 7, padc = -p.conv.pad;
+    const int padc = -p.conv.pad;
+    if (KS == 3 && p.conv.tclass == 2) {
+      // heaviest tiles first (longest processing time first under dynamic dispatch): an XCD keeps the share of tiles the map above
+      // gives it -- q tiles, q / 8 of every class (the dispatcher sets tclass = 2 only where 64 divides tiles_m) -- but walks them by
+      // tap count: the 8-tap class, the three 4-tap classes, the three 2-tap ones, the 1-tap class.  A pure relabelling of tiles.
+      const int q = nblocks >> 3, pc = q >> 3;
+      const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+      const int rank = idx / pc, u = idx - rank * pc;
+      const int two = (0x01243567u >> (4 * rank)) & 7;       // axes (z, y, x) on which the class has two taps: 7, 6, 5, 3, 4, 2, 1, 0
+      const int cls_h = (padc & 1) ? two : two ^ 7;          // an axis has two taps where t0 == 0: parity == padc & 1
+      bm = xcd * (q / tiles_n) + (u / tiles_n) * 8 + cls_h;
+      bn = u % tiles_n;
+    }
+    const int cls = bm & 7;
     t0z = (((cls >> 2) & 1) + padc) & 1; t0y = (((cls >> 1) & 1) + padc) & 1; t0x = ((cls & 1) + padc) & 1;
     const int cz = t0z < KS ? (KS - t0z + 1) >> 1 : 0;
     cy = t0y < KS ? (KS - t0y + 1) >> 1 : 0; cx = t0x < KS ? (KS - t0x + 1) >> 1 : 0;
@@ -431,6 +452,29 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
       c_off[i] = ((bz * din + by) * din + bx) * p.conv.cin + alc[i] * 8;
     }
   }
+  // Loader 2 (the stem), the same diet.  A thread's chunks all sit in LDS column alc (row & 7 does not depend on i), so they share
+  // ONE tap sequence 8 kt + alc: the thread keeps that tap's (dz, dy, dx) and advances it by 8 taps per K-step with carries -- no
+  // division -- and a chunk is again an AND, a compare, an add and the selects against its validity mask and 32-bit base offset.
+  // Taps >= KS^3 (the K padding) end at dz == KS, a bit no mask has.
+  int sz = 0, sy = 0, sx = 0;
+  if (LOADER == 2) {
+    const int din = p.conv.din;
+    int t = k_begin * 8 + alc[0];
+    sx = t % KS; t /= KS; sy = t % KS; sz = t / KS;
+    if (sz > KS) sz = KS;
+#pragma unroll
+    for (int i = 0; i < A_CH; ++i) {
+      unsigned m = 0;
+#pragma unroll
+      for (int a = 0; a < KS; ++a) {
+        m |= ((unsigned)(az[i] + a) < (unsigned)din ? 1u : 0u) << a;
+        m |= ((unsigned)(ay[i] + a) < (unsigned)din ? 1u : 0u) << (8 + a);
+        m |= ((unsigned)(ax[i] + a) < (unsigned)din ? 1u : 0u) << (16 + a);
+      }
+      c_msk[i] = m;
+      c_off[i] = ((az[i] * din + ay[i]) * din + ax[i]) * 8;
+    }
+  }
 
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
@@ -478,15 +522,18 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
       }
     } else {
       const int din = p.conv.din;
+      const unsigned sel = (1u << sz) | (1u << (8 + sy)) | (1u << (16 + sx));
+      const int toff = ((sz * din + sy) * din + sx) * 8;
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        const int tap = kt * 8 + alc[i];
-        const int dz = tap / (KS * KS), dy = (tap / KS) % KS, dx = tap % KS;
-        const int iz = az[i] + dz, iy = ay[i] + dy, ix = ax[i] + dx;
-        const bool ok = tap < KS * KS * KS && (unsigned)iz < (unsigned)din && (unsigned)iy < (unsigned)din && (unsigned)ix < (unsigned)din;
-        const half_t* src = ok ? p.A + ((size_t)(iz * din + iy) * din + ix) * 8 : p.conv.zero_page;
+        const half_t* src = (c_msk[i] & sel) == sel ? p.A + (c_off[i] + toff) : p.conv.zero_page;
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(sa + i * (NW * 1024)), 16, 0, 0);
       }
+      // the next K-step's tap is 8 further on: 8 = (Q2 KS + Q1) KS + Q0
+      constexpr int Q0 = 8 % KS, Q1 = (8 / KS) % KS, Q2 = 8 / (KS * KS);
+      sx += Q0; if (sx >= KS) { sx -= KS; ++sy; }
+      sy += Q1; if (sy >= KS) { sy -= KS; ++sz; }
+      sz += Q2; if (sz > KS) sz = KS;
     }
 #pragma unroll
     for (int i = 0; i < B_CH; ++i)
@@ -574,7 +621,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_nt_pipe_kernel(GemmParams p,
       }
     return;
   }
-  gemm_epilogue<BM, BN, BF, 2, tclass>(p, acc, smem, bm, bn, lane, wave, Mg, Ng, C32g, ldc32g);
+  gemm_epilogue<BM, BN, BF, 2, RMAP>(p, acc, smem, bm, bn, lane, wave, Mg, Ng, C32g, ldc32g);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -856,7 +903,8 @@ static void gemm_manifest(neraf_ctx* ctx, const GemmParams& p, int loader, int s
   else
     snprintf(nm, sizeof(nm), "%s<%d, %d | %s M=%d N=%d K=%d%s",      // the streaming body's template arguments are <N, K, ...>
              stream ? "gemm_f16_nt_stream_kernel" : (wide ? "gemm_f16_nt_wide_kernel" : "gemm_f16_nt_pipe_kernel"), bm, bn,
-             loader == 0 ? "plain" : (p.conv.tflip ? "dgrad" : "conv"), p.M, p.N, p.K, splits > 1 ? " splitK" : "");
+             p.conv.tclass == 3 ? "dgrad s2 compact" : (loader == 0 ? "plain" : (p.conv.tflip ? "dgrad" : "conv")), p.M, p.N, p.K,
+             splits > 1 ? " splitK" : "");
   if (splits > 1) {
     neraf_node(ctx, nm, flops, rA + rB, slabs);
     neraf_node(ctx, "splitk_reduce_kernel | K-split slabs -> result", 0.0, slabs + epi_r, epi_w);
@@ -1665,6 +1713,8 @@ __global__ __launch_bounds__(256) void wgrad_grouped_reduce_kernel(WgTable t, Wg
 // shorter chain saves (NERAF_SPLIT_MIN_K overrides, for measurements)
 static const int kWide = [] { const char* e = getenv("NERAF_GEMM_WIDE"); return e ? atoi(e) : 1; }();
 static const int kSplitMinK = [] { const char* e = getenv("NERAF_SPLIT_MIN_K"); return e ? atoi(e) : 32; }();
+// largest 64x64-tile count of a plain GEMM that still takes the 32x32 form (0: off); see dispatch_tile
+static const int kTile32 = [] { const char* e = getenv("NERAF_TILE32"); return e ? atoi(e) : 128; }();
 
 // NERAF_CONV_WAVES=8: the implicit-GEMM convolutions' 64x64 tiles on 8 waves per workgroup (gemm_f16_nt_pipe_kernel NW)
 static bool conv_waves8() { static const bool v = [] { const char* e = getenv("NERAF_CONV_WAVES"); return e && atoi(e) == 8; }(); return v; }
@@ -1679,10 +1729,38 @@ int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
   // alternate tile by tile, so every XCD's share of the grid holds the same mix
   static const int kTclass = [] { const char* e = getenv("NERAF_DGRAD_TCLASS"); return e ? atoi(e) : 1; }();
   p.conv.tclass = 0;
+  if constexpr (LOADER == 1 && KS == 1) {
+    // strided 1x1x1 dgrad added in place: its one tap reaches the even voxels only and the other seven classes ARE the destination, so
+    // only the reaching class is launched -- a plain GEMM over the din^3 source rows whose epilogue lands row r on voxel (2z, 2y, 2x)
+    // (out_row, RMAP 2), in the tile shape the dispatcher gives a plain GEMM of that size.  Same K order per element as a class-0
+    // tile of the parity-class form: the same bits.  NERAF_DGRAD_COMPACT=0 restores the eight-class launch (A/B).
+    static const int kCompact = [] { const char* e = getenv("NERAF_DGRAD_COMPACT"); return e ? atoi(e) : 1; }();
+    const int h = p.conv.din, rows = h * h * h;
+    if (kCompact && p.conv.tstride == 2 && p.conv.tflip && p.conv.pad == 0 && p.conv.dout == 2 * h && p.ngroups <= 1 &&
+        p.M == 8 * rows && (rows % 64) == 0 && (p.Npad % 64) == 0 && p.lda == p.conv.cin && p.K == p.conv.cin && p.C16 &&
+        p.add16 == p.C16 && p.ldadd == p.ldc16 && !p.lmask && !p.C16T && !p.C32 && !p.colsum && !p.colsumsq && !p.bnb_x && !p.bnb_mask) {
+      p.conv.tclass = 3;
+      p.M = p.Mpad = rows;
+      const int ntiles = (rows / 64) * (p.Npad / 64);
+      if (kTile32 && ntiles <= kTile32) return launch_pipe<32, 32, 4, 0, 1, BF, true>(ctx, p, 1, stream);
+      return launch_pipe<64, 64, 4, 0, 1, BF, true>(ctx, p, 1, stream);
+    }
+  }
   if (LOADER == 1 && kTclass && p.conv.tstride == 2 && p.conv.tflip && (p.conv.dout & 1) == 0 && p.ngroups <= 1 &&
       p.Mpad == p.conv.dout * p.conv.dout * p.conv.dout && (p.Mpad % 512) == 0 && (p.Npad % 64) == 0 && !p.lmask && !p.C16T && !p.C32 &&
       !p.colsum && !p.colsumsq) {
-    p.conv.tclass = 1;
+    // tclass 2: each XCD walks its tiles heaviest class first (see the kernel); needs whole groups of 8 tiles_n tiles per XCD
+    static const int kHeavyFirst = [] { const char* e = getenv("NERAF_DGRAD_HEAVY_FIRST"); return e ? atoi(e) : 1; }();
+    if constexpr (LOADER == 1 && KS == 3) {
+      // parity-class launches of at most NERAF_DGRAD_TILE32 (256) 64x64 tiles run on 32x32 tiles: all of them are resident at once, so the
+      // launch lasts as long as its 8-tap tiles, and those are shorter (4096 x 256 x 6912: 19.6 -> 15.7 us); 0: never
+      static const int kTclass32 = [] { const char* e = getenv("NERAF_DGRAD_TILE32"); return e ? atoi(e) : 256; }();
+      if (kTclass32 && (p.Mpad / 64) * (p.Npad / 64) <= kTclass32) {
+        p.conv.tclass = (kHeavyFirst && ((p.Mpad / 32) % 64) == 0) ? 2 : 1;
+        return launch_pipe<32, 32, 4, LOADER, KS, BF, true>(ctx, p, 1, stream);
+      }
+    }
+    p.conv.tclass = (KS == 3 && kHeavyFirst && ((p.Mpad / 64) % 64) == 0) ? 2 : 1;
     if constexpr (LOADER == 1) { if (conv_waves8()) return launch_pipe<64, 64, 4, LOADER, KS, BF, true, 8>(ctx, p, 1, stream); }
     return launch_pipe<64, 64, 4, LOADER, KS, BF, LOADER == 1>(ctx, p, 1, stream);
   }
@@ -1749,7 +1827,6 @@ int dispatch_tile(neraf_ctx* ctx, const GemmParams& p_in, hipStream_t stream) {
   // per 16 KiB K-step, cold or L2-warm operands alike), so the K loop is bound by how many CUs pull: 32x32 tiles on 4x the
   // workgroups run it at 0.164 us per K-step -- 512 x 256 x 1024: 7.9 -> 5.8 us, 4096 x 128 x 512: 5.9 -> 4.9 us
   // (tools/small_gemm_bench.py), step -0.05 ms.  NERAF_TILE32 = largest 64x64-tile count that still takes the 32x32 form (0: off).
-  static const int kTile32 = [] { const char* e = getenv("NERAF_TILE32"); return e ? atoi(e) : 128; }();
   if constexpr (LOADER == 0) {
     if (ng > 1) {
       if (kTile32 && splits == 1 && ntiles <= kTile32) return launch_pipe<32, 32, 4, LOADER, KS, BF, false, 4, true>(ctx, p, 1, stream);

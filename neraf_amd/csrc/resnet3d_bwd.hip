@@ -517,15 +517,20 @@ __global__ void set_f32x2_kernel(float* p, float a, float b) { if (threadIdx.x =
 __global__ void set_u64_kernel(unsigned long long* p, unsigned long long v) { if (threadIdx.x == 0 && blockIdx.x == 0) p[0] = v; }
 
 // stem input gradient for a window of cells: dgrid[c][cell] = sum_taps sum_co dY[(z+2-dz)/2,...][co] W[co][c][tap] / S.
-// One wave per cell, lanes over the 64 output channels; the weights are first re-laid as Wt[tap][c][co] so that every load of
-// the inner loop is one coalesced row (W[co][c][tap] would cost 64 cache lines per load instruction).
+// One wave per cell, lanes over the 64 output channels; the weights are read as Wt[tap][c][co] fp32 (every load one coalesced row;
+// W[co][c][tap] would cost 64 cache lines per load instruction), a layout the backward's weight-pack launch writes into the stem's
+// slot of the packed blob (stem_wt_relayout below; the stem has no dgrad GEMM, so the slot is otherwise unused).
 __global__ __launch_bounds__(256) void stem_w_relayout_kernel(const float* __restrict__ W, float* __restrict__ Wt) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;          // over [125][8][64]
-  if (idx >= 125 * 8 * 64) return;
-  const int co = idx & 63, c = (idx >> 6) & 7, tap = idx >> 9;
-  Wt[idx] = c < 7 ? W[((size_t)co * 7 + c) * 125 + tap] : 0.f;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < kStemWtElems) stem_wt_relayout(W, Wt, idx);
 }
 
+// The taps that reach a cell are known from its parity: per axis dz = t0 + 2 j with t0 = (z + pad) & 1 = z & 1, j = 0 .. 2 - t0, from
+// source voxel ((z + 2 - t0) >> 1) - j.  All 27 (jz, jy, jx) are walked without a branch: coordinates are clamped into the tensor
+// and the table, every dY row of the cell is requested before the first FMA and the weights a z-plane (63 rows) at a time, and a
+// tap outside the filter or the tensor leaves the accumulators as they are (a select on a wave-uniform flag).  The reaching taps
+// are added in ascending (dz, dy, dx) order, one FMA chain per lane and channel, then the 64 lanes by shuffles: the order -- and
+// so every bit -- of the per-tap loop this replaces (one dependent dY load and seven dependent weight loads per reaching tap).
 __global__ __launch_bounds__(256) void stem_dgrid_kernel(const half_t* __restrict__ dy, const float* __restrict__ Wt, int S, int dout,
                                                         const unsigned long long* __restrict__ start_dev, int n, int nch,
                                                         const float* __restrict__ inv_scale, float* __restrict__ dgrid) {
@@ -534,19 +539,49 @@ __global__ __launch_bounds__(256) void stem_dgrid_kernel(const half_t* __restric
   if (i >= n) return;
   const size_t cell = (size_t)start_dev[0] + i;   // device-side so that the captured launch sequence does not depend on the window
   const int x = (int)(cell % S), y = (int)((cell / S) % S), z = (int)(cell / ((size_t)S * S));
-  float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int dz = 0; dz < 5; ++dz) {
-    const int nz = z + 2 - dz; if (nz < 0 || (nz & 1) || (nz >> 1) >= dout) continue;
-    for (int dyy = 0; dyy < 5; ++dyy) {
-      const int ny = y + 2 - dyy; if (ny < 0 || (ny & 1) || (ny >> 1) >= dout) continue;
-      for (int dx = 0; dx < 5; ++dx) {
-        const int nx = x + 2 - dx; if (nx < 0 || (nx & 1) || (nx >> 1) >= dout) continue;
-        const float d = (float)dy[((size_t)((nz >> 1) * dout + (ny >> 1)) * dout + (nx >> 1)) * 64 + lane];
-        const float* w = Wt + (size_t)((dz * 5 + dyy) * 5 + dx) * 512 + lane;
+  const int t0z = z & 1, t0y = y & 1, t0x = x & 1;
+  const int bz = (z + 2 - t0z) >> 1, by = (y + 2 - t0y) >> 1, bx = (x + 2 - t0x) >> 1;
+  bool okz[3], oky[3], okx[3];
+  int sz[3], sy[3], sx[3], tz[3], ty[3], tx[3];            // clamped source coordinate and clamped tap index per axis
 #pragma unroll
-        for (int c = 0; c < 7; ++c) if (c < nch) acc[c] = fmaf(d, w[c * 64], acc[c]);
+  for (int j = 0; j < 3; ++j) {
+    const int az = bz - j, ay = by - j, ax = bx - j;
+    okz[j] = t0z + 2 * j < 5 && az >= 0 && az < dout; oky[j] = t0y + 2 * j < 5 && ay >= 0 && ay < dout; okx[j] = t0x + 2 * j < 5 && ax >= 0 && ax < dout;
+    sz[j] = min(max(az, 0), dout - 1); sy[j] = min(max(ay, 0), dout - 1); sx[j] = min(max(ax, 0), dout - 1);
+    tz[j] = min(t0z + 2 * j, 4); ty[j] = min(t0y + 2 * j, 4); tx[j] = min(t0x + 2 * j, 4);
+  }
+  half_t d[27];
+#pragma unroll
+  for (int jz = 0; jz < 3; ++jz)
+#pragma unroll
+    for (int jy = 0; jy < 3; ++jy)
+#pragma unroll
+      for (int jx = 0; jx < 3; ++jx)
+        d[(jz * 3 + jy) * 3 + jx] = dy[((size_t)(sz[jz] * dout + sy[jy]) * dout + sx[jx]) * 64 + lane];
+  float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int jz = 0; jz < 3; ++jz) {
+    float w[9][7];
+#pragma unroll
+    for (int jy = 0; jy < 3; ++jy)
+#pragma unroll
+      for (int jx = 0; jx < 3; ++jx) {
+        const float* wp = Wt + (size_t)((tz[jz] * 5 + ty[jy]) * 5 + tx[jx]) * 512 + lane;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) w[jy * 3 + jx][c] = wp[c * 64];
       }
-    }
+#pragma unroll
+    for (int jy = 0; jy < 3; ++jy)
+#pragma unroll
+      for (int jx = 0; jx < 3; ++jx) {
+        const bool ok = okz[jz] && oky[jy] && okx[jx];
+        const float dv = (float)d[(jz * 3 + jy) * 3 + jx];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+          const float a = fmaf(dv, w[jy * 3 + jx][c], acc[c]);
+          acc[c] = (ok && c < nch) ? a : acc[c];
+        }
+      }
   }
 #pragma unroll
   for (int c = 0; c < 7; ++c) {
@@ -576,7 +611,7 @@ struct BwdLayout {
   size_t dy[64];              // dY of every convolution [rows_pad(dout)][cout] fp16: all alive until the grouped weight-gradient launch
   size_t gm, da;              // masked g (identity residual), d(a1|a2) scratch
   size_t dpost;               // fp32 [din1^3][64] stem
-  size_t wtmp;                // fp32 [cout][tap*cin + c] weight gradients before the layout change (k > 1 convs)
+  size_t wtmp;                // 256 KB no launch uses any more (the stem's Wt table moved into the packed blob); the offsets after it stay put
   size_t splitk; size_t splitk_bytes;
   size_t total;
 };
@@ -626,7 +661,7 @@ void make_bwd_layout(const Arch& A, BwdLayout* L) {
       max_act = std::max(max_act, rows_out * c.cout * 2);
       max_act = std::max(max_act, rows_in * c.cin * 2);
     }
-    max_wtmp = std::max(max_wtmp, (size_t)125 * 8 * 64 * 4);      // Wt[tap][c][co] of the stem (stem_dgrid_kernel)
+    max_wtmp = std::max(max_wtmp, (size_t)125 * 8 * 64 * 4);
   }
   for (int i = 0; i < 2; ++i) L->g[i] = take(max_act);
   for (int i = 0; i < A.nconv; ++i) L->dy[i] = take(rows_pad(A.conv[i].dout) * A.conv[i].cout * 2);
@@ -716,6 +751,9 @@ inline bool fuse_bn_sums(const ConvSpec& bn_conv) {
   return on && (long)cube(bn_conv.dout) <= max_vox && (bn_conv.cout % 64) == 0;
 }
 
+// the stem is the 7 -> 64 channel 5x5x5 convolution stem_dgrid_kernel is written for: its Wt table is part of the packed blob
+inline bool stem_wt_packed(const Arch& A) { return A.conv[0].k == 5 && A.conv[0].cin_real == 7 && A.conv[0].cout == 64; }
+
 // dX [din^3][cin] = conv_transpose(dY [dout^3][cout], W) (+ add16).  bn_ci >= 0: the result is the gradient w.r.t. relu(bn_{bn_ci}(.))
 // (+ residual), `bn_act` that post-activation tensor: the epilogue masks the result with it and reduces the two
 // BatchNorm-backward sums of conv bn_ci into its accumulators.  The result (and add16) live in dy's scale group: ratio 1.
@@ -800,7 +838,15 @@ extern "C" int neraf_resnet3d_pack_weights_bwd(neraf_ctx* ctx, const neraf_resne
   bt.tile_begin[bt.n] = tiles;
   if (t.n > 0)
     if (int e = launch_pack_dgrad(ctx, t, acc, max_taps, (char*)packed_t, st)) return e;
+  // the stem's fp32 Wt[tap][c][co] for stem_dgrid_kernel, in the stem's (otherwise unused) slot of the blob: extra workgroups of
+  // the brick launch, or a launch of its own where no convolution takes the brick packer
+  const bool stem_wt = stem_wt_packed(A);
+  if (stem_wt && bt.n == 0) {
+    hipLaunchKernelGGL(stem_w_relayout_kernel, dim3((kStemWtElems + 255) / 256), dim3(256), 0, st, conv_w[0], (float*)((char*)packed_t + B.wt[0]));
+    NERAF_HIP_CHECK(ctx, hipGetLastError());
+  }
   if (bt.n > 0) {
+    if (stem_wt) { bt.stem_w = conv_w[0]; bt.stem_off = B.wt[0]; tiles += (kStemWtElems + 1023) / 1024; }
     const size_t lds = brick_lds_bytes(max_run);
     static size_t attr_lds = 0;
     if (lds > attr_lds) {
@@ -910,13 +956,15 @@ static int resnet3d_bwd_body(neraf_ctx* ctx, const Arch& A, const Layout& L, con
     if (int e = bn_backward(c, 0, dpost, nullptr, nullptr, dy0, nullptr, k_g, k_s, -1)) return e;      // relu mask already applied by the routing
     items[n_items++] = wgrad_item(c, 0, dy0, (const half_t*)(ws + L.x0), k_s);
     if (n_cells > 0) {
-      float* Wt = (float*)(bws + B.wtmp);
-      hipLaunchKernelGGL(stem_w_relayout_kernel, dim3((125 * 8 * 64 + 255) / 256), dim3(256), 0, st, conv_w[0], Wt);
+      if (!stem_wt_packed(A)) return neraf_fail(ctx, NERAF_EINVAL, "resnet3d_bwd: the grid gradient needs the 7 -> 64 channel 5x5x5 stem");
+      // Wt[tap][c][co]: written by neraf_resnet3d_pack_weights_bwd into the stem's slot of the packed blob
+      const float* Wt = (const float*)((const char*)packed_t + B.wt[0]);
       hipLaunchKernelGGL(stem_dgrid_kernel, dim3((n_cells + 3) / 4), dim3(256), 0, st, dy0, Wt, A.S, c0.dout,
                          reinterpret_cast<const unsigned long long*>(bws + B.scale + 64), n_cells, n_ch, c.inv(k_s), dgrid_cells);
       NERAF_HIP_CHECK(ctx, hipGetLastError());
-      neraf_node(ctx, "stem_w_relayout_kernel | W[co][c][tap] -> Wt[tap][c][co]", 0.0, 125.0 * 7 * 64 * 4, 125.0 * 8 * 64 * 4);
-      neraf_node(ctx, "stem_dgrid_kernel | grid gradient of the refresh window", 2.0 * n_cells * (125.0 / 8.0) * 64 * n_ch, (double)n_cells * (125.0 / 8.0) * 128.0,
+      // per cell: 27 dY rows of 128 bytes and 27 x 7 weight rows of 256 bytes requested (the table itself is 224 KB, L2-resident)
+      neraf_node(ctx, "stem_dgrid_kernel | grid gradient of the refresh window", 2.0 * n_cells * (125.0 / 8.0) * 64 * n_ch,
+                 (double)n_cells * 27.0 * 128.0 + 125.0 * 7 * 64 * 4,
                  (double)n_cells * n_ch * 4.0);
     }
   }
@@ -1137,5 +1185,95 @@ extern "C" int neraf_debug_conv_bn_relu_stage(neraf_ctx* ctx, int cin, int cin_r
   NERAF_HIP_CHECK(ctx, hipStreamSynchronize(st));
   (void)wl;
   (void)hipFree(ws); (void)hipFree(bws); (void)hipFree(packed); (void)hipFree(packed_t); (void)hipFree(extra);
+  return NERAF_OK;
+}
+
+// Test entry: the raw stem convolution (7 -> 64 channels, 5x5x5, stride 2, pad 2: conv loader 2) on caller data, straight into the
+// caller's buffers.  x fp16 [din^3][8] (only the first cin_real channels carry weights), w fp32 [64][cin_real][125];
+// y fp16 [din^3 / 8 rounded up to 128 rows][64] (rows past the result are written as zeros), sums fp32 [2][128] = column sums and
+// sums of squares of the result (the fused BatchNorm statistics, one replica, cleared here).
+extern "C" int neraf_debug_stem_conv(neraf_ctx* ctx, int din, int cin_real, const void* x_f16, const float* w, void* y_f16, float* sums,
+                                     neraf_stream_t stream) {
+  if (!x_f16 || !w || !y_f16 || !sums || din < 2 || din > 256 || (din & 1) || cin_real < 1 || cin_real > 8)
+    return neraf_fail(ctx, NERAF_EINVAL, "debug_stem_conv: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const ConvSpec c{8, 64, 5, 2, 2, din, din / 2, cin_real};
+  const size_t wbytes = (size_t)conv_npad(c) * conv_kpad(c) * 2;
+  char *packed = nullptr, *zero = nullptr;
+  NERAF_HIP_CHECK(ctx, hipMalloc(&packed, wbytes));
+  NERAF_HIP_CHECK(ctx, hipMalloc(&zero, 256));
+  NERAF_HIP_CHECK(ctx, hipMemsetAsync(zero, 0, 256, st));
+  NERAF_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, 256 * 4, st));
+  PackTable t{};
+  t.n = 1; t.src[0] = w; t.begin[0] = 0; t.dst_off[0] = 0; t.cout[0] = 64; t.cin_real[0] = cin_real; t.cin[0] = 8;
+  t.taps[0] = 125; t.kpad[0] = conv_kpad(c); t.begin[1] = (unsigned long long)conv_npad(c) * conv_kpad(c);
+  hipLaunchKernelGGL(pack_all_conv_weights_kernel, dim3((unsigned)((t.begin[1] + 255) / 256)), dim3(256), 0, st, t, packed);
+  GemmParams g{};
+  g.A = (const half_t*)x_f16; g.lda = 8;
+  g.B = (const half_t*)packed; g.ldb = conv_kpad(c);
+  g.M = (int)cube(c.dout); g.N = 64; g.K = conv_kpad(c); g.Mpad = (int)rows_pad(c.dout); g.Npad = 64; g.alpha = 1.f; g.tile_n = 64;
+  g.C16 = (half_t*)y_f16; g.ldc16 = 64;
+  g.colsum = sums; g.colsumsq = sums + 128;
+  g.conv.loader = 2; g.conv.din = din; g.conv.dout = c.dout; g.conv.stride = 2; g.conv.pad = 2; g.conv.ksize = 5; g.conv.cin = 8;
+  g.conv.zero_page = (const half_t*)zero;
+  const int e = launch_gemm_f16(ctx, g, st);
+  NERAF_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  (void)hipFree(packed); (void)hipFree(zero);
+  return e;
+}
+
+// Test entry: a raw stride-2 transposed convolution (the dgrad GEMM of a k^3, stride-2, pad k/2 convolution cin -> cout whose input
+// edge is din) on caller data.  dy fp16 [(din/2)^3][cout], w fp32 [cout][cin][k^3]; dx fp16 [din^3][cin] (din^3 a multiple of 128):
+// in_place != 0 adds the result into dx (add16 == destination: what the residual branch's dgrad does), else dx is overwritten.
+extern "C" int neraf_debug_conv_transpose(neraf_ctx* ctx, int cin, int cout, int k, int din, const void* dy_f16, const float* w,
+                                          void* dx_f16, int in_place, neraf_stream_t stream) {
+  if (!dy_f16 || !w || !dx_f16 || (k != 1 && k != 3) || din < 2 || din > 64 || (din & 1) || (cube(din) % 128) || cin < 64 || (cin % 64) ||
+      cout < 64 || (cout % 64))
+    return neraf_fail(ctx, NERAF_EINVAL, "debug_conv_transpose: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  Arch A{};
+  A.S = din; A.nconv = 1; A.nblock = 0; A.pooled = din; A.final_edge = din; A.n_features = 1024;
+  A.conv[0] = ConvSpec{cin, cout, k, 2, k / 2, din, din / 2, cin};
+  Layout L{}; BwdLayout B{};
+  make_layout(A, &L);
+  make_bwd_layout(A, &B);
+  char *ws = nullptr, *bws = nullptr, *packed_t = nullptr;
+  NERAF_HIP_CHECK(ctx, hipMalloc(&ws, L.total));
+  NERAF_HIP_CHECK(ctx, hipMalloc(&bws, B.total));
+  NERAF_HIP_CHECK(ctx, hipMalloc(&packed_t, B.packed_total + 256));
+  NERAF_HIP_CHECK(ctx, hipMemsetAsync(ws + L.zero_page, 0, 256, st));
+  PackTTable t{};
+  const int nrows = cin == 64 ? 64 : round_up(cin, 128);
+  t.n = 1; t.src[0] = w; t.tile_begin[0] = 0; t.dst_off[0] = B.wt[0]; t.cout[0] = cout; t.cin[0] = cin; t.taps[0] = k * k * k;
+  t.kcols[0] = t.taps[0] * cout; t.nrows[0] = nrows;
+  t.tile_begin[1] = (cout / 32) * (nrows / 32);
+  int e = launch_pack_dgrad(ctx, t, t.tile_begin[1], t.taps[0], packed_t, st);
+  if (!e) {
+    Ctx c{ctx, st, &A, &L, &B, packed_t, ws, bws, nullptr, nullptr, nullptr};
+    e = conv_dgrad(c, 0, (const half_t*)dy_f16, in_place ? (const half_t*)dx_f16 : nullptr, (half_t*)dx_f16);
+  }
+  NERAF_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  (void)hipFree(ws); (void)hipFree(bws); (void)hipFree(packed_t);
+  return e;
+}
+
+// Test entry: the stem's grid gradient (stem_dgrid_kernel) for the window of n_cells cells from cell `start` of the S^3 grid (cell =
+// (z S + y) S + x), on caller data: dy fp16 [(S/2)^3][64] (gradient w.r.t. the stem convolution's output), w fp32 [64][7][125];
+// out fp32 [n_ch][n_cells] = inv_scale * the transposed convolution at those cells, channels 0 .. n_ch - 1.
+extern "C" int neraf_debug_stem_dgrid(neraf_ctx* ctx, int S, const void* dy_f16, const float* w, unsigned long long start, int n_cells,
+                                      int n_ch, float inv_scale, float* out, neraf_stream_t stream) {
+  if (!dy_f16 || !w || !out || S < 2 || S > 256 || (S & 1) || n_cells < 1 || n_ch < 1 || n_ch > 7 || start + (size_t)n_cells > cube(S))
+    return neraf_fail(ctx, NERAF_EINVAL, "debug_stem_dgrid: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  char* tmp = nullptr;                         // [0, 8): start, [64, 72): inv_scale, [256, ...): Wt
+  NERAF_HIP_CHECK(ctx, hipMalloc(&tmp, 256 + (size_t)kStemWtElems * 4));
+  hipLaunchKernelGGL(set_u64_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long*>(tmp), start);
+  hipLaunchKernelGGL(set_f32x2_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<float*>(tmp + 64), inv_scale, 0.f);
+  hipLaunchKernelGGL(stem_w_relayout_kernel, dim3((kStemWtElems + 255) / 256), dim3(256), 0, st, w, reinterpret_cast<float*>(tmp + 256));
+  hipLaunchKernelGGL(stem_dgrid_kernel, dim3((n_cells + 3) / 4), dim3(256), 0, st, (const half_t*)dy_f16, reinterpret_cast<const float*>(tmp + 256),
+                     S, S / 2, reinterpret_cast<const unsigned long long*>(tmp), n_cells, n_ch, reinterpret_cast<const float*>(tmp + 64), out);
+  NERAF_HIP_CHECK(ctx, hipGetLastError());
+  NERAF_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  (void)hipFree(tmp);
   return NERAF_OK;
 }

@@ -281,7 +281,15 @@ __global__ __launch_bounds__(256) void pack_all_conv_weights_kernel(PackTable t,
 //   MODE 0  forward layout   fp16  dst[co][tap*cin + ci]     CIB = cin: a brick is COB complete destination rows (contiguous)
 //   MODE 1  dgrad layout     fp16  dst[ci][tap*cout + co]    COB = cout: every (ci, tap) run is a complete row segment of cout
 // (the first version used [32 co][32 ci] bricks for both: 64-byte destination runs, 2 TB/s).  COB / CIB come from brick_shape().
+// fp32 Wt[tap][c][co] of the stem filter W[co][7][125] (c = 7: zeros): what stem_dgrid_kernel reads
+constexpr int kStemWtElems = 125 * 8 * 64;
+__device__ __forceinline__ void stem_wt_relayout(const float* __restrict__ W, float* __restrict__ Wt, int idx) {   // idx over [125][8][64]
+  const int co = idx & 63, c = (idx >> 6) & 7, tap = idx >> 9;
+  Wt[idx] = c < 7 ? W[((size_t)co * 7 + c) * 125 + tap] : 0.f;
+}
+
 struct BrickTable {
+  const float* stem_w; unsigned long long stem_off;   // MODE 1: workgroups past the last brick write the stem's Wt at this offset (null: none)
   int n;
   const float* src[kMaxConv];
   int tile_begin[kMaxConv + 1];                // prefix of (cout/COB)*(cin/CIB) bricks
@@ -294,6 +302,14 @@ __global__ __launch_bounds__(256) void pack_bricks_kernel(BrickTable t, char* __
   extern __shared__ unsigned short brick16[];          // [COB co][pitch]
   int lo = 0, hi = t.n - 1;
   const int bid = blockIdx.x;
+  if (MODE == 1 && bid >= t.tile_begin[t.n]) {         // the stem's table, 1024 elements per workgroup
+    float* Wt = reinterpret_cast<float*>(packed + t.stem_off);
+    for (int e = threadIdx.x; e < 1024; e += 256) {
+      const int idx = (bid - t.tile_begin[t.n]) * 1024 + e;
+      if (idx < kStemWtElems) stem_wt_relayout(t.stem_w, Wt, idx);
+    }
+    return;
+  }
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t.tile_begin[mid] <= bid) lo = mid; else hi = mid - 1; }
   const int i = lo;
   const int tile = bid - t.tile_begin[i];
